@@ -15,6 +15,14 @@ the RCCL all-reduce (N > 1), the fused AdamW update and the metrics fold.
     python bench.py --gpus 8                       # 8 local ranks, one per GPU (built-in launcher)
     torchrun --nproc-per-node 8 bench.py --gpus 8  # the same job under torchrun
     python bench.py --strategy fsdp|pp             # the other two tutorials
+    python bench.py --full                         # + the untimed extras (below)
+    python bench.py --dump-outputs DIR             # + the last timed step's state as DIR/*.npy
+
+A plain run only sets up, warms up, times ``--steps`` steps and prints the JSON
+line.  ``--full`` adds, after the timed region, the per-step latency pass
+(``details.p50_ms`` / ``p90_ms``), the step collective's device time
+(``details.collective_ms_p50``) and, at N > 1, the all-reduce transport sweep
+(``details.comm_sweep``); without it those fields are null.
 
 ``--gpus N`` is enforced: without torchrun the script starts N ranks itself
 (runtime/launch.py, before any GPU call); under a launcher it exits non-zero
@@ -344,6 +352,39 @@ def _mlp2_launches(eng, tx_: str, spg: int) -> str:
     return f"1 (run-ahead mlp2_bwd{tx_})"
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all files of one rank together
+
+
+def timed_outputs(tr) -> dict:
+    """What a caller of the timed path holds after its last step, as host float32 arrays:
+    this rank's parameters (fp32 masters; FSDP: its shards), the optimizer moments and the
+    accumulated (loss sum, count, ...) metrics."""
+    st = tr.state
+    P = st.extra["sharded"].local if "sharded" in st.extra else st.params
+    n = P.numel
+    out = {"params": P.master[:n], "metrics": tr.gather_metrics() if hasattr(tr, "gather_metrics") else tr.metrics}
+    for k, name in (("m", "adam_m"), ("v", "adam_v"), ("buf", "sgd_buf")):
+        if torch.is_tensor(st.opt_state.get(k)):
+            out[name] = st.opt_state[k][:n]
+    return {k: v.detach().float().cpu().numpy().ravel() for k, v in out.items()}
+
+
+def dump_outputs(arrays: dict, outdir: str, rank: int = 0, budget: int = DUMP_BUDGET_BYTES):
+    """Write ``outdir/<name>.npy`` (rank r > 0: ``<name>_rank<r>.npy``), float32.  An array
+    over its share of ``budget`` is written as a fixed sample: the elements at sorted indices
+    drawn without replacement by ``numpy.random.default_rng(0)`` -- the same elements in every
+    run and every build."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    share = budget // (4 * max(1, len(arrays)))   # elements per file
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(outdir, f"{name}.npy" if rank == 0 else f"{name}_rank{rank}.npy"), a)
+
+
 def pick_steps_per_graph(steps: int, cap: int) -> int:
     """Steps per captured graph: all of them when steps <= cap (one replay, one host
     launch for the whole timed region), else the largest divisor of steps <= cap
@@ -384,8 +425,15 @@ def main():
     ap.add_argument("--steps-per-graph", type=int, default=None,
                     help="complete training steps recorded per hipGraph (amortises the replay launch); default: "
                          "all timed steps in one graph when --steps <= 200 (DP), else the largest divisor <= the cap")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the untimed extras: the per-step latency pass (p50 / p90), "
+                         "the step collective's device time and, at N > 1, the all-reduce transport sweep")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left -- this rank's parameters, optimizer "
+                         "moments and metrics -- as DIR/<name>.npy (float32; a fixed seeded sample of an array "
+                         "beyond its share of 64 MB)")
     ap.add_argument("--no-comm-sweep", action="store_true",
-                    help="skip the untimed RCCL-vs-xGMI all-reduce sweep reported for N > 1")
+                    help="--full: skip the untimed RCCL-vs-xGMI all-reduce sweep reported for N > 1")
     ap.add_argument("--optimizer", choices=["adamw", "sgd"], default="adamw",
                     help="DP: adamw (the reference's optax.adamw) or sgd (the fused SGD kernel)")
     ap.add_argument("--autotune", choices=["auto", "off"], default="auto",
@@ -478,9 +526,11 @@ def main():
         dt = float(t.item())
     if ws > 1 and on_gpu:
         comm_check(tr, "timed steps")
-    # per-step latency distribution (separate, untimed pass)
+    if args.dump_outputs:
+        dump_outputs(timed_outputs(tr), args.dump_outputs, D.rank())
+    # --full: per-step latency distribution (separate, untimed pass)
     p50 = p90 = None
-    if on_gpu:
+    if on_gpu and args.full:
         ts = []
         for _ in range(min(50, args.steps)):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -492,9 +542,9 @@ def main():
         ts.sort()
         p50, p90 = ts[len(ts) // 2], ts[int(0.9 * len(ts))]
     coll_ms = sweep = None
-    if hasattr(tr, "time_collective"):
+    if args.full and hasattr(tr, "time_collective"):
         coll_ms = tr.time_collective(batch, iters=min(20, max(5, args.steps)))
-    if on_gpu and ws > 1 and args.strategy == "dp" and not args.no_comm_sweep:
+    if args.full and on_gpu and ws > 1 and args.strategy == "dp" and not args.no_comm_sweep:
         sweep = comm_sweep(tr, dev)
     if hasattr(tr, "finalize"):
         tr.finalize()

@@ -17,6 +17,22 @@ def test_pick_steps_per_graph_divides_the_timed_steps():
     assert bench.pick_steps_per_graph(0, 200) == 1
 
 
+def test_dump_outputs_writes_float32_and_a_fixed_sample_of_large_arrays(tmp_path):
+    import numpy as np
+
+    small = np.arange(10, dtype=np.float64)
+    big = np.arange(1000, dtype=np.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs({"small": small, "big": big}, str(tmp_path / d), budget=2 * 4 * 100)   # 100 elements each
+    a, b = (np.load(tmp_path / d / "big.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (100,) and np.array_equal(a, b)   # the same sample every time
+    assert np.all(np.diff(a) > 0) and set(a) <= set(big)
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small)
+    bench.dump_outputs({"small": small}, str(tmp_path / "a"), rank=1)
+    assert np.array_equal(np.load(tmp_path / "a" / "small_rank1.npy"), small)
+
+
 def test_mlp2_launches_names_the_persistent_kernel_only_when_it_runs():
     pst = types.SimpleNamespace(pst_ok=True)
     one = types.SimpleNamespace(pst_ok=False)
