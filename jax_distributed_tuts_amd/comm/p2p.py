@@ -24,11 +24,11 @@ import torch
 import torch.distributed as dist
 
 from ..ops import _lib
+from .ipc_context import IpcContext
 from .xgmi import TICKS_PER_S, requested
 
 log = logging.getLogger(__name__)
 
-HANDLE_BYTES = 64
 MAX_SLOTS = 64
 
 _lib.declare("jdt_p2p_create", c_int, [c_int, c_int, c_long, c_int, ctypes.POINTER(c_void_p), c_void_p])
@@ -47,48 +47,31 @@ def wire_bytes(t: torch.Tensor) -> int:
     return (t.numel() * t.element_size() + 15) // 16 * 16
 
 
-class XgmiP2P:
+class XgmiP2P(IpcContext):
     def __init__(self, group, rank: int, world: int, slot_bytes: int, n_slots: int, device: torch.device,
                  timeout_s: float = 30.0, self_test: bool = True):
         if not 0 < n_slots <= MAX_SLOTS:
             raise ValueError(f"1..{MAX_SLOTS} slots")
-        self.group, self.rank, self.world, self.device = group, rank, world, device
+        super().__init__(group, rank, world, device)
         self.n_slots = n_slots
         self.timeout = c_longlong(int(timeout_s * TICKS_PER_S))
-        self.ctx = c_void_p()
-        self.ok = False
         L = _lib.lib()
         # a sender writes into the receiver's slot: every member uses the largest request
         sizes = [0] * world
         dist.all_gather_object(sizes, int(slot_bytes), group=group)
         slot_bytes = max(sizes)
-        h = (ctypes.c_char * (2 * HANDLE_BYTES))()
-        with torch.cuda.device(device):
-            rc = L.jdt_p2p_create(rank, world, int(slot_bytes), int(n_slots), ctypes.byref(self.ctx), h)
-        objs = [None] * world
-        dist.all_gather_object(objs, bytes(h) if rc == 0 else None, group=group)
-        good = all(o is not None for o in objs)
-        if good:
-            allh = b"".join(objs)
-            buf = ctypes.create_string_buffer(allh, len(allh))
-            with torch.cuda.device(device):
-                good = L.jdt_p2p_open(self.ctx, buf) == 0
-            if not good:
-                log.warning("p2p: hipIpcOpenMemHandle failed on rank %d", rank)
-        else:
-            log.warning("p2p: inbox export failed on some rank (rank %d rc %d)", rank, rc)
-        good = self._agree(good)
+        good = self._handshake(
+            lambda h: L.jdt_p2p_create(rank, world, int(slot_bytes), int(n_slots), ctypes.byref(self.ctx), h),
+            lambda allh: L.jdt_p2p_open(self.ctx, allh), 2, "p2p")
         if good and self_test:
             good = self._agree(self._self_test())
-        self.ok = good
-        if not good:
-            self.close()
+        self._finish(good)
 
-    def _agree(self, ok: bool) -> bool:
-        t = torch.tensor([1 if ok else 0], dtype=torch.int32,
-                         device=self.device if dist.get_backend(self.group) == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MIN, group=self.group)
-        return bool(int(t.item()))
+    def _unmap(self):
+        _lib.lib().jdt_p2p_unmap(self.ctx)
+
+    def _destroy(self):
+        _lib.lib().jdt_p2p_destroy(self.ctx)
 
     @property
     def slot_bytes(self) -> int:
@@ -118,18 +101,6 @@ class XgmiP2P:
     def error(self) -> int:
         """1 if a receive of this rank timed out (synchronises the device)."""
         return int(_lib.lib().jdt_p2p_error(self.ctx)) if self.ctx else 0
-
-    def close(self, collective: bool = True):
-        """Two-phase teardown (collective over the pipe group; comm/xgmi.py close)."""
-        if self.ctx:
-            if collective:
-                from .xgmi import ipc_teardown_barrier
-
-                _lib.lib().jdt_p2p_unmap(self.ctx)
-                ipc_teardown_barrier(self.group)
-            _lib.lib().jdt_p2p_destroy(self.ctx)
-            self.ctx = c_void_p()
-        self.ok = False
 
     def __del__(self):
         try:

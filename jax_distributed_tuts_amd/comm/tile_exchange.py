@@ -22,13 +22,12 @@ from ctypes import c_int, c_longlong, c_void_p
 from typing import Optional
 
 import torch
-import torch.distributed as dist
 
 from ..ops import _lib
+from .ipc_context import IpcContext, agree  # noqa: F401  (agree: the trainers' collective verdicts)
 
 log = logging.getLogger(__name__)
 
-HANDLE_BYTES = 64
 TICKS_PER_S = 100_000_000   # s_memrealtime: 100 MHz
 # payload per tile (floats): 7 dW1 sub-tiles of 256, then dW2 / db1 (256 each) and
 # 128 for db2 + the metric slots -- ops/csrc/mlp_fused.hip tx_tile callers
@@ -48,45 +47,28 @@ _lib.declare("jdt_md_tx_ok", c_int, [c_int, c_int])
 SELFTEST_TILES = 64   # 64 workgroups per rank: 8 ranks' self-test grids fit one shared GPU
 
 
-class TileExchange:
+class TileExchange(IpcContext):
     """IPC inboxes of the per-tile exchange between the ``world`` ranks of ``group``
     (collective: every rank constructs it at the same point).  ``ok`` is False on every
-    rank if any rank failed to export or map them."""
+    rank if any rank failed to export or map them.  No finaliser: an exchange is released
+    by its trainer's collective ``close`` only."""
 
     def __init__(self, group, rank: int, world: int, tiles: int, device: torch.device,
                  pay: int = TILE_PAYLOAD, timeout_s: float = 10.0):
-        self.group, self.rank, self.world, self.tiles, self.pay = group, rank, world, tiles, pay
+        super().__init__(group, rank, world, device)
+        self.tiles, self.pay = tiles, pay
         self.timeout_s = float(timeout_s)
-        self.device = device
-        self.ctx = c_void_p()
-        self.ok = False
         self.selftest = None
         L = _lib.lib()
-        h = (ctypes.c_char * (3 * HANDLE_BYTES))()
-        with torch.cuda.device(device):
-            rc = L.jdt_tx_create(rank, world, tiles, pay, ctypes.byref(self.ctx), h)
-        mine = bytes(h) if rc == 0 else None
-        objs = [None] * world
-        dist.all_gather_object(objs, mine, group=group)
-        good = all(o is not None for o in objs)
-        if good:
-            allh = b"".join(objs)
-            buf = ctypes.create_string_buffer(allh, len(allh))
-            with torch.cuda.device(device):
-                good = L.jdt_tx_open(self.ctx, buf, int(timeout_s * TICKS_PER_S)) == 0
-            if not good:
-                log.warning("tile exchange: hipIpcOpenMemHandle failed on rank %d", rank)
-        else:
-            log.warning("tile exchange: buffer export failed on some rank (rank %d rc %d)", rank, rc)
-        good = self._agree(good)
+        good = self._handshake(
+            lambda h: L.jdt_tx_create(rank, world, tiles, pay, ctypes.byref(self.ctx), h),
+            lambda allh: L.jdt_tx_open(self.ctx, allh, int(timeout_s * TICKS_PER_S)), 3, "tile exchange")
         if good:
             # every rank exchanges known values through the real buffers and kernel code
             # (all payload positions, W-rank sums bit-exact), then clears its flags -- the
             # step kernels' epochs start at 1 -- before any rank may use them
             good = self._self_test()
-        self.ok = self._agree(good)
-        if not self.ok:
-            self.close()
+        self._finish(self._agree(good))
 
     def _self_test(self) -> bool:
         L = _lib.lib()
@@ -103,9 +85,6 @@ class TileExchange:
             return False
         return True
 
-    def _agree(self, ok: bool) -> bool:
-        return agree(self.group, ok, self.device)
-
     @property
     def args_ptr(self) -> int:
         """Device pointer of the kernel's TxArgs (Mlp2Args::tx)."""
@@ -115,25 +94,11 @@ class TileExchange:
         """This rank's error word (4: an exchange wait timed out; synchronous read)."""
         return int(_lib.lib().jdt_tx_error(self.ctx)) if self.ctx else 0
 
-    def close(self, collective: bool = True):
-        """Two-phase teardown (collective over the group; comm/xgmi.py close)."""
-        if self.ctx:
-            if collective:
-                from .xgmi import ipc_teardown_barrier
+    def _unmap(self):
+        _lib.lib().jdt_tx_unmap(self.ctx)
 
-                _lib.lib().jdt_tx_unmap(self.ctx)
-                ipc_teardown_barrier(self.group)
-            _lib.lib().jdt_tx_close(self.ctx)
-            self.ctx = c_void_p()
-        self.ok = False
-
-
-def agree(group, ok: bool, device: torch.device) -> bool:
-    """AND of ``ok`` over ``group`` (collective)."""
-    t = torch.tensor([1 if ok else 0], dtype=torch.int32,
-                     device=device if dist.get_backend(group) == "nccl" else "cpu")
-    dist.all_reduce(t, op=dist.ReduceOp.MIN, group=group)
-    return bool(int(t.item()))
+    def _destroy(self):
+        _lib.lib().jdt_tx_close(self.ctx)
 
 
 def ahead_tx_ok(rows: int, hidden: int, ranks_on_this_gpu: int, k_in: int = 784) -> bool:
@@ -162,6 +127,22 @@ def fx_owner_span(world: int, rows: int = 784, chunk: int = 112) -> int:
         return 1 << 30
     rpq = rows // world
     return max((c0 + chunk - 1) // rpq - c0 // rpq + 1 for c0 in range(0, rows, chunk))
+
+
+def renew_for(old: Optional[TileExchange], mesh, axis: str, device: torch.device, tiles: int, local_ok: bool):
+    """(a new exchange or None, ranks sharing this GPU) once every rank of ``axis``
+    agrees it can take the one-launch step (``local_ok``: this rank's verdict), else
+    (None, 1) with ``old`` untouched.  ``old`` -- the dropped engine's -- is closed first:
+    every engine gets fresh buffers, since their flags hold epochs (optimizer step + 1),
+    which a checkpoint restore (invalidate -> new engine) may move backwards.  Collective."""
+    if not agree(mesh.group(axis), local_ok, device):
+        return None, 1
+    if old is not None:
+        torch.cuda.synchronize(device)
+        old.close()
+    from ..runtime.dist import ranks_per_gpu
+
+    return create_for(mesh, axis, device, tiles=tiles), ranks_per_gpu()   # (cached: no collective here)
 
 
 def create_for(mesh, axis: str, device: torch.device, tiles: int) -> Optional[TileExchange]:

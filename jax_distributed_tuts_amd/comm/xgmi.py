@@ -39,10 +39,10 @@ import torch
 import torch.distributed as dist
 
 from ..ops import _lib
+from .ipc_context import IpcContext, ipc_teardown_barrier  # noqa: F401  (re-exported)
 
 log = logging.getLogger(__name__)
 
-HANDLE_BYTES = 64
 TICKS_PER_S = 100_000_000  # s_memrealtime
 
 
@@ -115,18 +115,6 @@ _lib.declare("jdt_xgmi_destroy", c_int, [c_void_p])
 _lib.declare("jdt_xgmi_unmap", c_int, [c_void_p])
 
 
-def ipc_teardown_barrier(group):
-    """The barrier between the two phases of a comm context's teardown: every rank of
-    ``group`` has closed its mappings of the peers' buffers before any rank releases its
-    own (a gloo group's barrier runs on the host; nccl's on the device)."""
-    if group is None or not dist.is_initialized():
-        return
-    if dist.get_backend(group) == "nccl":
-        from ..runtime.dist import device
-
-        dist.barrier(group=group, device_ids=[device().index])
-    else:
-        dist.barrier(group=group)
 _lib.declare("jdt_xgmi_seg_slice", c_long, [c_long])
 _lib.declare("jdt_ipc_pool_stats", None, [c_void_p])
 
@@ -224,50 +212,31 @@ def requested(mode: str, world: int, device: torch.device) -> bool:
     return True
 
 
-class XgmiComm:
+class XgmiComm(IpcContext):
     _serial = 0   # contexts created in this process (self-test failure logs)
 
     def __init__(self, group, rank: int, world: int, cap_floats: int, device: torch.device,
                  timeout_s: float = 30.0, self_test: bool = True):
         XgmiComm._serial += 1
-        self.group, self.rank, self.world, self.device = group, rank, world, device
+        super().__init__(group, rank, world, device)
         self.timeout = c_longlong(int(timeout_s * TICKS_PER_S))
-        self.ctx = c_void_p()
-        self.ok = False
         L = _lib.lib()
         if (L.jdt_xgmi_adam_size() != ctypes.sizeof(XgAdam) or L.jdt_xgmi_segs_size() != ctypes.sizeof(XgSegs)
                 or L.jdt_xgmi_fsdp_size() != ctypes.sizeof(XgFsdp)):
             raise RuntimeError("XgAdam layout mismatch between Python and comm/csrc/xgmi.hip")
-        h = (ctypes.c_char * (3 * HANDLE_BYTES))()
-        with torch.cuda.device(device):
-            rc = L.jdt_xgmi_create(rank, world, int(cap_floats), ctypes.byref(self.ctx), h)
-        mine = bytes(h) if rc == 0 else None
-        objs = [None] * world
-        dist.all_gather_object(objs, mine, group=group)
-        good = all(o is not None for o in objs)
-        if good:
-            allh = b"".join(objs)
-            buf = ctypes.create_string_buffer(allh, len(allh))
-            with torch.cuda.device(device):
-                rc = L.jdt_xgmi_open(self.ctx, buf)
-            good = rc == 0
-            if not good:
-                log.warning("xgmi: hipIpcOpenMemHandle failed on rank %d (rc %d)", rank, rc)
-        else:
-            log.warning("xgmi: buffer export failed on some rank (rank %d rc %d)", rank, rc)
-        good = self._agree(good)
+        good = self._handshake(
+            lambda h: L.jdt_xgmi_create(rank, world, int(cap_floats), ctypes.byref(self.ctx), h),
+            lambda allh: L.jdt_xgmi_open(self.ctx, allh), 3, "xgmi")
         if good and self_test:
             good = self._agree(self._self_test())
-        self.ok = good
-        if not good:
-            self.close()
+        self._finish(good)
 
     # ------------------------------------------------------------------ plumbing
-    def _agree(self, ok: bool) -> bool:
-        t = torch.tensor([1 if ok else 0], dtype=torch.int32,
-                         device=self.device if dist.get_backend(self.group) == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MIN, group=self.group)
-        return bool(int(t.item()))
+    def _unmap(self):
+        _lib.lib().jdt_xgmi_unmap(self.ctx)
+
+    def _destroy(self):
+        _lib.lib().jdt_xgmi_destroy(self.ctx)
 
     @property
     def capacity(self) -> int:
@@ -313,19 +282,6 @@ class XgmiComm:
         info = self.error_info()
         if info is not None:
             raise RuntimeError(f"xgmi collective timed out on this rank (peer dead or desynchronised): {info}")
-
-    def close(self, collective: bool = True):
-        """Two-phase teardown (collective over the context's group): every rank closes its
-        mappings of the peers' buffers, a barrier, then every rank releases its own -- no
-        peer mapping outlives the pages it resolves to (comm/csrc/ipc_pool.hip).
-        ``collective=False`` (garbage collection): one phase, this rank only."""
-        if self.ctx:
-            if collective:
-                _lib.lib().jdt_xgmi_unmap(self.ctx)
-                ipc_teardown_barrier(self.group)
-            _lib.lib().jdt_xgmi_destroy(self.ctx)
-            self.ctx = c_void_p()
-        self.ok = False
 
     def __del__(self):
         try:

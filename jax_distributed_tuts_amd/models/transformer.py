@@ -295,7 +295,7 @@ class TransformerLM:
         """The deferred weight gradients of every microbatch in one GEMM per weight:
         dW (+)= A^T . dZ over all T = n_mb * mb rows of ``arena`` (``opt``: AdamW in the
         epilogue, each weight's single gradient contribution of the step).  ``on(j)``:
-        context for GEMM j (parallel.pipeline._MbStreams: the GEMMs touch disjoint
+        context for GEMM j (parallel.step_program._MbStreams: the GEMMs touch disjoint
         weights and only read the step counter, so they may run on several streams)."""
         if opt is not None:
             opt.only_contribution = True

@@ -22,7 +22,6 @@ dropout streams are indexed differently) -- 4x fewer launches.
 """
 from __future__ import annotations
 
-import contextlib
 import os
 from dataclasses import dataclass, field
 from typing import Optional
@@ -35,8 +34,9 @@ from ..ops import kernels as K
 from ..runtime.dist import Mesh
 from ..utils import rng as R
 from ..utils.flat import FlatParams, N_METRIC_SLOTS
-from ..utils.profiling import named_scope, replay_scope
-from ..utils.train_state import AdamW, Batch, TrainState, check_static_batch, load_static_batch
+from ..utils.profiling import named_scope
+from ..utils.train_state import AdamW, Batch, TrainState
+from .step_program import CapturedStep, hw_queues, mb_streams
 
 
 def fold_rng_over_axis(rng: int, mesh: Optional[Mesh], axis_name: str) -> int:
@@ -85,10 +85,13 @@ class DPConfig:
     loop_streams: int = field(default_factory=lambda: int(os.environ.get("JDT_LOOP_STREAMS", "0")))
 
 
-class DataParallelTrainer:
+class DataParallelTrainer(CapturedStep):
     """Owns the step program for one rank; ``step(batch_local)`` = train_step_dp."""
 
+    scope = "train_step_dp"
+
     def __init__(self, state: TrainState, mesh: Optional[Mesh], cfg: DPConfig = DPConfig()):
+        CapturedStep.__init__(self)
         self.state = state
         self.mesh = mesh
         self.cfg = cfg
@@ -98,13 +101,13 @@ class DataParallelTrainer:
         self.world = C.axis_size(mesh, cfg.axis)
         # the step issues its gradient collective (N > 1, or a Mesh(unit_groups=True))
         self._coll = self.world > 1 or C.active(mesh, cfg.axis)
-        self.graph = None
-        self._ahead = None
-        self._static = None
         self.fused = None
+        self._stage = None    # the staged xGMI bucket's plan (_setup_stage)
+        self._txx = None      # the one-launch step's tile exchange (_tile_exchange)
         self._capturing = False
         self.buckets = None
         self._scan = None
+        self._mbt = None
         self._loop_engine = None
         self._loop_tried = False
         self._loop_streams = None
@@ -129,9 +132,7 @@ class DataParallelTrainer:
         graphs): called after a checkpoint restore; rebuilt on the next step."""
         self.fused = None
         self._stage = None
-        self.graph = None
-        self._ahead = None
-        self.multi = None
+        self._drop_graphs()
         self._scan = None
         self._capturing = False
         self._loop_engine = None
@@ -169,9 +170,8 @@ class DataParallelTrainer:
             return None, 1
         from ..comm import tile_exchange as TX
         from ..runtime.dist import ranks_per_gpu
-        from .fused_mlp import _is_adamw, _is_plain_sgd, deterministic, supported
-
-        from .fused_mlp import FusedMLPDeep, supported_deep
+        from .fused_mlp import (FusedMLPDeep, _is_adamw, _is_plain_sgd, deterministic, md_ahead_ok, supported,
+                                supported_deep)
 
         share = ranks_per_gpu()
         dev = batch.inputs.device
@@ -191,20 +191,13 @@ class DataParallelTrainer:
             # per-GPU variants spill registers), one rank per GPU unmeasured
             local = (os.environ.get("JDT_DP_DEEP_TX", "0") == "1" and not deterministic()
                      and _is_adamw(self.state.tx) and os.environ.get("JDT_MLP2_AHEAD", "1") == "1"
-                     and bool(_lib_md_ahead_ok(batch.size)) and TX.deep_tx_ok(batch.size, share))
+                     and bool(md_ahead_ok(batch.size)) and TX.deep_tx_ok(batch.size, share))
             tiles = FusedMLPDeep.tx_tiles(self.model.L - 1)
         else:
             local, tiles = False, 0
-        if not TX.agree(self.mesh.group(self.cfg.axis), local, dev):
-            return None, 1
-        # fresh buffers per engine: their flags hold epochs (optimizer step + 1), which a
-        # checkpoint restore (invalidate -> new engine) may move backwards
-        old = getattr(self, "_txx", None)
-        if old is not None:
-            torch.cuda.synchronize(batch.inputs.device)
-            old.close()
-        self._txx = TX.create_for(self.mesh, self.cfg.axis, dev, tiles=tiles)
-        return self._txx, share
+        tx, share = TX.renew_for(self._txx, self.mesh, self.cfg.axis, dev, tiles, local)
+        self._txx = tx or self._txx   # (no agreement: the old one stays, for close())
+        return tx, share
 
     def _setup_stage(self):
         """N > 1 with the fused xGMI all-reduce + AdamW: the backward kernel writes the
@@ -243,20 +236,15 @@ class DataParallelTrainer:
             # the reference's minibatch loop (util.py:41-78) on the fused per-layer
             # kernels: fwd + CE/bwd per minibatch, grads accumulated into P.grad
             k = loop_eng.n_sets
-            main = torch.cuda.current_stream(P.master.device) if k > 1 else None
-            if k > 1:
-                if self._loop_streams is None:
-                    self._loop_streams = [torch.cuda.Stream(P.master.device) for _ in range(k - 1)]
-                for s_ in self._loop_streams:
-                    s_.wait_stream(main)
+            on = mb_streams(self._loop_streams, k, P.master.device)
+            self._loop_streams = on.side or self._loop_streams
+            on.fork()
             for i in range(n_mb):
-                ctx = torch.cuda.stream(self._loop_streams[i % k - 1]) if (k > 1 and i % k) else contextlib.nullcontext()
-                with ctx:
+                with on(i):
                     loop_eng.forward(i, batch.inputs[i * mb:(i + 1) * mb])
                     loop_eng.backward(i, labels=batch.labels[i * mb:(i + 1) * mb])
+            on.join()
             if k > 1:
-                for s_ in self._loop_streams:
-                    main.wait_stream(s_)
                 loop_eng.merge()
             return
         if cfg.accum == "fused":
@@ -272,8 +260,6 @@ class DataParallelTrainer:
                                 on_ready=bk.ready if (bk is not None and last) else None)
 
     def _loop_sets(self) -> int:
-        from .pipeline import hw_queues
-
         k = int(self.cfg.loop_streams)
         return min(k if k > 0 else (2 if self.model.L >= 3 else 1), hw_queues())
 
@@ -302,7 +288,7 @@ class DataParallelTrainer:
     # the same masks as the unrolled loop (util.py:81-137 vs 41-78: the
     # reference's scan indexes its per-minibatch rngs with the traced loop index).
     def _mb_tensors(self):
-        if getattr(self, "_mbt", None) is None:
+        if self._mbt is None:
             dev = self.state.params.master.device
             self._mbt = (torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
         return self._mbt
@@ -369,7 +355,7 @@ class DataParallelTrainer:
             return
         with named_scope("sync_grads"):
             if self.xg is not None:
-                if self._xg_fused_opt and getattr(self, "_stage", None) is not None:
+                if self._xg_fused_opt and self._stage is not None:
                     tx, st = self.state.tx, self.state.opt_state
                     self.xg.all_reduce_adamw_staged_(
                         self._stage, p=P.master, m=st["m"], v=st["v"], shadow=P.shadow, n_params=P.numel,
@@ -390,25 +376,14 @@ class DataParallelTrainer:
             else:
                 C.psum_(P.grad, self.mesh, self.cfg.axis)
 
-    def update(self):
-        self.update_noncounting()
-        self.state.step += 1
-
-    def step(self, batch: Batch):
-        if self.graph is not None:
-            check_static_batch(self._static, batch)
-            self._replay()
-            return
+    def _eager_step(self, batch: Batch):
         self.compute(batch)
         self.sync()
-        self.update()
+        self.update_noncounting()
 
-    def set_batch(self, batch: Batch):
-        """New data for captured graphs: copied into the captured batch tensors (the
-        run-ahead schedule's next forward, computed from the old contents, is redone)."""
-        if self._static is None:
-            return
-        load_static_batch(self._static, batch, (self.fused,))
+    @property
+    def _batch_engines(self):
+        return (self.fused,)
 
     # ------------------------------------------------------------------ hipGraph
     def capture(self, batch: Batch, capture_collectives: bool = False, steps_per_graph: int = 1):
@@ -425,58 +400,42 @@ class DataParallelTrainer:
         assert batch.inputs.is_cuda
         from ..runtime.dist import collectives_capturable
 
-        self._static = batch
         self._capturing = True  # from now on the step's collectives are whole-buffer (no per-bucket overlap)
         # the collective inside the step graph: xGMI collectives are kernels, RCCL enqueues
         # on the capturing stream (reference: the whole step under one jit,
         # data_paral.py:241-251); only a gloo group runs it on the host between graphs
         one_graph = (not self._coll or capture_collectives or self.xg is not None or collectives_capturable())
-        if one_graph:
-            def body():
-                self.compute(batch)
-                self.sync()
-                self.update_noncounting()
 
-            g = capture_graph(body)
-            if g is None:   # the collective refused capture: compute / RCCL eager / update graphs
-                self._capture_split(batch)
-                return
-            self.graph = ("one", g)
-            self.multi = None
-            self._ahead = None
-            # single GPU, whole-step fused engine: the S steps are ONE persistent launch
-            # (opt-in mlp2_loop_kernel, grid barriers instead of kernel boundaries) or,
-            # by default, one run-ahead launch per step (step t's backward + AdamW +
-            # step t+1's forward).  Run-ahead graphs come in two variants: "cold" starts
-            # with step t's forward, "primed" does not -- after a run-ahead launch the
-            # forward of the next step is already done (FusedMLP2.ahead_primed).
-            loop = self.world == 1 and getattr(self.fused, "loop_ok", False)
-            ahead = (self.world == 1 or self.one_launch) and not loop and getattr(self.fused, "ahead_ok", False)
-            if ahead:
-                from .fused_mlp import AheadGraphs
+        def body():
+            self.compute(batch)
+            self.sync()
+            self.update_noncounting()
 
-                self._ahead = AheadGraphs(self.fused, batch, steps_per_graph, pool=g.pool())
-                if steps_per_graph > 1:
-                    self.multi = (steps_per_graph, self._ahead.graph(steps_per_graph))
-            elif steps_per_graph > 1:
-                gm = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gm, pool=g.pool()):
-                    if not (loop and self.fused.run_loop(batch, steps_per_graph)):
-                        for _ in range(steps_per_graph):
-                            body()
-                self.multi = (steps_per_graph, gm)
-        else:
-            self._capture_split(batch)
+        # single GPU, whole-step fused engine: the S steps are ONE persistent launch
+        # (opt-in mlp2_loop_kernel, grid barriers instead of kernel boundaries) or,
+        # by default, one run-ahead launch per step (step t's backward + AdamW +
+        # step t+1's forward).  Run-ahead graphs come in two variants: "cold" starts
+        # with step t's forward, "primed" does not -- after a run-ahead launch the
+        # forward of the next step is already done (FusedMLP2.ahead_primed).
+        def loop():
+            return self.world == 1 and getattr(self.fused, "loop_ok", False)
 
-    def _capture_split(self, batch: Batch):
+        def ahead():
+            ok = (self.world == 1 or self.one_launch) and not loop() and getattr(self.fused, "ahead_ok", False)
+            return self.fused if ok else None
+
+        if one_graph and self._capture(body, batch, steps_per_graph, ahead,
+                                       lambda: loop() and self.fused.run_loop(batch, steps_per_graph)):
+            return
+        # a gloo group, or the collective refused capture: compute / eager collective / update graphs
         g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(g1):
             self.compute(batch)
         with torch.cuda.graph(g2):
             self.update_noncounting()
+        self._static = batch
         self.graph = ("split", g1, g2)
-        self.multi = None
-        self._ahead = None
+        self.multi = self._ahead = None
 
     def update_noncounting(self):
         P = self.state.params
@@ -530,12 +489,9 @@ class DataParallelTrainer:
         and the captured graphs, so another trainer can be built in this process
         (bench.py's probes).  Collective (runtime.dist.quiesce: no rank frees buffers a
         peer's kernel may still write); the trainer is unusable afterwards."""
-        from ..runtime.dist import quiesce
+        from ..runtime.dist import quiesce_and_close
 
-        quiesce(self.state.params.master.device)
-        for r in (getattr(self, "_txx", None), self.xg):
-            if r is not None:
-                r.close()
+        quiesce_and_close(self.state.params.master.device, self._txx, self.xg)
         self._txx = self.xg = None
         self.invalidate()
 
@@ -545,64 +501,17 @@ class DataParallelTrainer:
             return "none"
         if self.xg is not None:
             return "xgmi"
-        from ..runtime.dist import backend
+        from ..runtime.dist import backend_name
 
-        b = backend()
-        return "rccl" if b == "nccl" else (b or "none")
+        return backend_name()
 
-    def run_steps(self, batch: Batch, n: int):
-        """n training steps; with a multi-step graph, n // S replays of it plus
-        single-step replays for the remainder."""
-        multi = getattr(self, "multi", None)
-        if self.graph is not None:
-            check_static_batch(self._static, batch)
-        if self.graph is not None and multi is not None:
-            S, gm = multi
-            for _ in range(n // S):
-                with replay_scope("train_step_dp", S):
-                    self._ahead.replay(S) if self._ahead else gm.replay()
-            self.state.step += (n // S) * S
-            n = n % S
-        for _ in range(n):
-            self.step(batch)
-
-    def _replay(self):
-        kind = self.graph[0]
-        if kind == "one" and getattr(self, "_ahead", None):
-            with replay_scope("train_step_dp"):
-                self._ahead.replay(1)
-        elif kind == "one":
-            with replay_scope("train_step_dp"):
-                self.graph[1].replay()
-        else:
+    def _replay(self, S: int = 1):
+        if self.graph[0] == "split":   # the gloo collective runs on the host between the two graphs
             self.graph[1].replay()
             self.sync()
             self.graph[2].replay()
-        self.state.step += 1
-
-
-def _lib_md_ahead_ok(rows: int) -> int:
-    from ..ops import _lib
-
-    return _lib.lib().jdt_md_ahead_ok(int(rows))
-
-
-def capture_graph(body, pool=None) -> Optional[torch.cuda.CUDAGraph]:
-    """``body`` recorded into a hipGraph, or None if a collective in it refused stream
-    capture (the caller then keeps that collective eager).  RCCL collectives enqueue
-    on the capturing stream and are recorded like kernels."""
-    g = torch.cuda.CUDAGraph()
-    try:
-        with torch.cuda.graph(g, pool=pool):
-            body()
-    except RuntimeError as e:
-        import logging
-
-        logging.getLogger(__name__).warning("step capture with the collective inside failed (%s); "
-                                            "running the collective eagerly between graphs", e)
-        torch.cuda.synchronize()
-        return None
-    return g
+        else:
+            super()._replay(S)
 
 
 def train_step_dp(trainer: DataParallelTrainer, batch: Batch):

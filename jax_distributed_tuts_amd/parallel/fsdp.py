@@ -30,7 +30,6 @@ from __future__ import annotations
 
 import logging
 import math
-import contextlib
 import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -45,8 +44,9 @@ from ..ops import kernels as K
 from ..runtime.dist import Mesh
 from ..utils import rng as R
 from ..utils.flat import FlatParams, ParamSpec, N_METRIC_SLOTS
-from ..utils.profiling import named_scope, replay_scope
-from ..utils.train_state import AdamW, Batch, TrainState, check_static_batch, load_static_batch
+from ..utils.profiling import named_scope
+from ..utils.train_state import AdamW, Batch, TrainState
+from .step_program import CapturedStep, hw_queues, mb_streams
 
 log = logging.getLogger("jdt.fsdp")
 
@@ -421,8 +421,11 @@ class _LoopView:
         return self.sp.local.grad
 
 
-class FSDPTrainer:
+class FSDPTrainer(CapturedStep):
+    scope = "train_step_fsdp"
+
     def __init__(self, state: TrainState, mesh: Optional[Mesh], cfg: FSDPConfig = FSDPConfig()):
+        CapturedStep.__init__(self)
         self.state, self.mesh, self.cfg = state, mesh, cfg
         self.sp: ShardedFlatParams = state.extra["sharded"]
         self.model: MLP = state.apply_fn
@@ -433,13 +436,14 @@ class FSDPTrainer:
         # N > 1 schedule, RCCL calls included, on one GPU)
         self._n1 = not (self.world > 1 or C.active(mesh, cfg.axis))
         self.fused = None
-        self.graph = None
-        self._ahead = None
-        self.multi = None
-        self._plan = None
+        self._txx = None          # the one-launch step's tile exchange (_tile_exchange)
+        self._plan = None         # the fused step collective's arguments (_fsdp_plan) ...
+        self._staged = False      # ... and whether the engine writes into its staging buffer
         self._full_fresh = True   # init_fsdp gathered the full shadow
         self._loop_engine = None
         self._loop_tried = False
+        self._loop_streams = None
+        self._shard_full = None   # the loop engine's full-grad ranges of the sharded leaves
         if self.world > 1 and self.sp.local.master.is_cuda and self.sp.xg is None:
             from ..comm.xgmi import create_for
 
@@ -455,9 +459,7 @@ class FSDPTrainer:
         self._loop_engine = None
         self._loop_tried = False
         self.fused = None
-        self.graph = None
-        self._ahead = None
-        self.multi = None
+        self._drop_graphs()
         self._plan = None
         self._full_fresh = False
 
@@ -482,8 +484,7 @@ class FSDPTrainer:
         from ..comm import tile_exchange as TX
         from ..runtime.dist import ranks_per_gpu
         from ..utils.train_state import AdamW
-        from .dp import _lib_md_ahead_ok
-        from .fused_mlp import FusedMLPDeep, deterministic, mlp2_chunk, supported, supported_deep
+        from .fused_mlp import FusedMLPDeep, deterministic, md_ahead_ok, mlp2_chunk, supported, supported_deep
 
         sp, W, dev = self.sp, self.world, batch.inputs.device
         share = ranks_per_gpu()
@@ -517,24 +518,19 @@ class FSDPTrainer:
             local = (base and os.environ.get("JDT_FSDP_DEEP_FX", "1") == "1"
                      and os.environ.get("JDT_MLP2_AHEAD", "1") == "1" and 784 % W == 0 and 512 % (16 * W) == 0
                      and TX.fx_owner_span(W, 784, 112) <= 2 and TX.fx_owner_span(W, 512, 64) <= 2
-                     and bool(_lib_md_ahead_ok(batch.size)) and TX.deep_fx_ok(batch.size, share))
+                     and bool(md_ahead_ok(batch.size)) and TX.deep_fx_ok(batch.size, share))
             tiles = FusedMLPDeep.tx_tiles(self.model.L - 1)
         else:
             local, tiles = False, 0
-        if not TX.agree(self.mesh.group(self.cfg.axis), local, dev):
-            return None, 1
-        old = getattr(self, "_txx", None)
-        if old is not None:
-            torch.cuda.synchronize(dev)
-            old.close()
-        self._txx = TX.create_for(self.mesh, self.cfg.axis, dev, tiles=tiles)
-        return self._txx, share
+        tx, share = TX.renew_for(self._txx, self.mesh, self.cfg.axis, dev, tiles, local)
+        self._txx = tx or self._txx   # (no agreement: the old one stays, for close())
+        return tx, share
 
     def _fsdp_plan(self):
         """Arguments of the fused FSDP step collective (comm/xgmi.py ``fsdp_plan``), or
         None when it does not apply: every sharded leaf must move on the segmented xGMI
         kernel, AdamW, <= 16 segments (JDT_FSDP_FUSED_COMM=0 turns it off)."""
-        if getattr(self, "_plan", None) is not None:
+        if self._plan is not None:
             return self._plan
         from ..utils.train_state import AdamW
 
@@ -558,7 +554,7 @@ class FSDPTrainer:
         """The fused engine writes its gradients straight into the collective's staging
         buffer (packed FSDP layout, step-parity half): the step's collective skips its
         staging copy -- the FSDP form of DP's staged bucket (JDT_FSDP_STAGED=0: off)."""
-        if (getattr(self, "_staged", False) or self._plan is None or self.fused is None
+        if (self._staged or self._plan is None or self.fused is None
                 or not hasattr(self.fused, "set_fsdp_stage") or os.environ.get("JDT_FSDP_STAGED", "1") == "0"):
             return
         sp = self.sp
@@ -576,10 +572,9 @@ class FSDPTrainer:
             return "none"
         if self.sp.xg is not None:
             return "xgmi"
-        from ..runtime.dist import backend
+        from ..runtime.dist import backend_name
 
-        b = backend()
-        return "rccl" if b == "nccl" else (b or "none")
+        return backend_name()
 
     @property
     def xgmi_status(self) -> str:
@@ -654,20 +649,9 @@ class FSDPTrainer:
             K.metrics_fold_(self.metrics, sp.local.metrics_slot)
         return True
 
-    def set_batch(self, batch: Batch):
-        """New data for captured graphs (see DataParallelTrainer.set_batch)."""
-        if getattr(self, "_static", None) is not None:
-            load_static_batch(self._static, batch, (self.fused, self._loop_engine))
-
-    def step(self, batch: Batch):
-        """train_step_fsdp (param_sharding.py:343-367)."""
-        if self.graph is not None:
-            check_static_batch(getattr(self, "_static", None), batch)
-            with replay_scope("train_step_fsdp"):
-                self._ahead.replay(1) if self._ahead else self.graph.replay()
-        else:
-            self._body(batch)
-        self.state.step += 1
+    @property
+    def _batch_engines(self):
+        return (self.fused, self._loop_engine)
 
     # ------------------------------------------------------------------ hipGraph
     @property
@@ -687,47 +671,18 @@ class FSDPTrainer:
         all-reduce, sharded AdamW, metrics fold) as a hipGraph; with
         ``steps_per_graph`` > 1 also a graph of that many consecutive steps."""
         assert self.capturable and batch.inputs.is_cuda
-        self._static = batch
         if not self._full_fresh:   # the fused step collective keeps the full shadow current
             self.sp.gather()
             self._full_fresh = True
-        from .dp import capture_graph
 
-        g = capture_graph(lambda: self._body(batch))
-        if g is None:   # a collective refused stream capture: the step stays eager
-            self.graph = None
-            return False
-        self.graph = g
         # N = 1 on the fused engine with AdamW in its epilogue: one run-ahead launch per
         # step (the DP engine's schedule, fused_mlp.AheadGraphs)
-        eng = self.fused
-        self._ahead = None
-        if (self._n1 or self.one_launch) and eng is not None and getattr(eng, "ahead_ok", False):
-            from .fused_mlp import AheadGraphs
+        def ahead():
+            ok = (self._n1 or self.one_launch) and getattr(self.fused, "ahead_ok", False)
+            return self.fused if ok else None
 
-            self._ahead = AheadGraphs(eng, batch, steps_per_graph, pool=g.pool())
-            if steps_per_graph > 1:
-                self.multi = (steps_per_graph, self._ahead.graph(steps_per_graph))
-        elif steps_per_graph > 1:
-            gm = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gm, pool=g.pool()):
-                for _ in range(steps_per_graph):
-                    self._body(batch)
-            self.multi = (steps_per_graph, gm)
-        return True
-
-    def run_steps(self, batch: Batch, n: int):
-        if self.graph is not None:
-            check_static_batch(getattr(self, "_static", None), batch)
-        if self.graph is not None and self.multi is not None:
-            S, gm = self.multi
-            for _ in range(n // S):
-                with replay_scope("train_step_fsdp", S):
-                    self._ahead.replay(S) if self._ahead else gm.replay()
-            self.state.step += (n // S) * S
-            n %= S
-        for _ in range(n):
-            self.step(batch)
+        # (False: a collective refused stream capture, the step stays eager)
+        return self._capture(lambda: self._eager_step(batch), batch, steps_per_graph, ahead)
 
     def _fused_loop(self, mb: int, seed: int):
         """FusedMLPStage (one stage = the whole classifier) on the _LoopView: minibatch
@@ -741,8 +696,6 @@ class FSDPTrainer:
             dev = sp.local.master.device
             coll_ok = self._n1 or (sp.xg is not None and len(sp._xg_names) == len(sp.sharded_names))
             if self.cfg.fused_loop and coll_ok and stage_supported(self.model, mb, dev):
-                from .pipeline import hw_queues
-
                 k = min(int(self.cfg.loop_streams) or (2 if self.model.L >= 3 else 1), hw_queues())
                 self._loop_engine = FusedMLPStage(self.model, _LoopView(sp), self.cfg.num_minibatches, mb,
                                                   self.state.step_tensor, seed,
@@ -752,8 +705,9 @@ class FSDPTrainer:
                 self._shard_full = [sp.full.grad[o:o + n] for o, n in offs]
         return self._loop_engine
 
-    def _body(self, batch: Batch):
-        """One step of device work (no host counters, so it can be captured)."""
+    def _eager_step(self, batch: Batch):
+        """train_step_fsdp (param_sharding.py:343-367): one step of device work (no host
+        counters, so it can be captured)."""
         if self._fused_step(batch):
             return
         st, sp, cfg = self.state, self.sp, self.cfg
@@ -768,17 +722,13 @@ class FSDPTrainer:
             # into the local shards (replicated leaves accumulate locally); then ONE
             # all-reduce of the local tail (replicated grads + metric slots), AdamW
             k = eng.n_sets   # > 1 only at N = 1: no collective inside the loop
-            main = torch.cuda.current_stream(batch.inputs.device) if k > 1 else None
-            if k > 1:
-                if getattr(self, "_loop_streams", None) is None:
-                    self._loop_streams = [torch.cuda.Stream(batch.inputs.device) for _ in range(k - 1)]
-                for s_ in self._loop_streams:
-                    s_.wait_stream(main)
+            on = mb_streams(self._loop_streams, k, batch.inputs.device)
+            self._loop_streams = on.side or self._loop_streams
+            on.fork()
             for i in range(n_mb):
                 if not self._n1 and (i == 0 or not cfg.gather_once):
                     sp.xg.all_gather_segments([(sp.full.s(n), sp.local.s(n)) for n in sp._xg_names])
-                with (torch.cuda.stream(self._loop_streams[i % k - 1]) if (k > 1 and i % k)
-                      else contextlib.nullcontext()):
+                with on(i):
                     eng.forward(i, batch.inputs[i * mb:(i + 1) * mb])
                     eng.backward(i, labels=batch.labels[i * mb:(i + 1) * mb])
                 if not self._n1 and (not cfg.scatter_once or i == n_mb - 1):
@@ -787,9 +737,8 @@ class FSDPTrainer:
                                                       accumulate=True)
                         for t in self._shard_full:
                             t.zero_()
+            on.join()
             if k > 1:
-                for s_ in self._loop_streams:
-                    main.wait_stream(s_)
                 eng.merge()
             if not self._n1:
                 sp.sync_replicated()
@@ -824,12 +773,9 @@ class FSDPTrainer:
     def close(self):
         """Release the IPC-mapped exchange buffers (tile exchange inboxes, the shards' xGMI
         context) and the captured graphs (see DataParallelTrainer.close; collective)."""
-        from ..runtime.dist import quiesce
+        from ..runtime.dist import quiesce_and_close
 
-        quiesce(self.sp.local.master.device)
-        for r in (getattr(self, "_txx", None), self.sp.xg):
-            if r is not None:
-                r.close()
+        quiesce_and_close(self.sp.local.master.device, self._txx, self.sp.xg)
         self._txx = self.sp.xg = None
         self.invalidate()
 

@@ -581,6 +581,11 @@ _lib.declare("jdt_md_fwd2", c_int, [ctypes.POINTER(MdArgs), ctypes.POINTER(MdArg
 DEEP_H = 512
 
 
+def md_ahead_ok(rows: int) -> int:
+    """Whether the deep engine's layer-0 backward can run ahead at ``rows`` rows."""
+    return _lib.lib().jdt_md_ahead_ok(int(rows))
+
+
 def supported_deep(model, rows: int, device) -> bool:
     """784 -> 512 x (L-1) -> 10 MLPs with L >= 3 (the 4-layer MLP of BASELINE configs #2/#3)."""
     from ..models.mlp import MLP
@@ -665,7 +670,7 @@ class FusedMLPDeep:
         self.ahead_ok = (self.fuse_opt and (self.world == 1 or tx is not None) and self.det_logits is None
                          and (self.mb_rows == 0 or os.environ.get("JDT_MLP2_AHEAD_MB", "0") == "1")
                          and m.dims[0] == 784 and os.environ.get("JDT_MLP2_AHEAD", "1") == "1"
-                         and bool(_lib.lib().jdt_md_ahead_ok(rows)))
+                         and bool(md_ahead_ok(rows)))
         self.ahead_primed = False
         self._ahead_args = None
         # dZ split (one GPU): the K-chunk workgroups of a column block share the dZ_i rows

@@ -23,7 +23,6 @@ bucket (grads + metric slots) per stage; the optimizer is the same fused AdamW.
 from __future__ import annotations
 
 import math
-import contextlib
 import os
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
@@ -37,8 +36,9 @@ from ..ops import kernels as K
 from ..runtime.dist import Mesh, is_initialized
 from ..utils import rng as R
 from ..utils.flat import FlatParams, N_METRIC_SLOTS
-from ..utils.profiling import named_scope, replay_scope
-from ..utils.train_state import AdamW, Batch, TrainState, check_static_batch, load_static_batch
+from ..utils.profiling import named_scope
+from ..utils.train_state import AdamW, Batch, TrainState
+from .step_program import CapturedStep, _MbStreams, hw_queues, mb_streams
 
 
 def split_layers(n_layers: int, n_stages: int) -> List[range]:
@@ -178,40 +178,7 @@ def _no_dropout(model) -> bool:
     return float(rate) == 0.0
 
 
-def hw_queues() -> int:
-    """HIP hardware queues per process (GPU_MAX_HW_QUEUES; HIP's default is 4), the cap
-    on concurrent-stream schedules.  ``JDT_HWQ_CAP=0`` lifts the cap (diagnosis of the
-    more-streams-than-queues case, tools/sessions/gpu_r4_hwq.sh)."""
-    if os.environ.get("JDT_HWQ_CAP", "1") == "0":
-        return 1 << 10
-    try:
-        return max(1, int(os.environ.get("GPU_MAX_HW_QUEUES", "4")))
-    except ValueError:
-        return 4
-
-
-class _MbStreams:
-    """``with on(i)``: run work item i on stream i % k (item 0, k, 2k, ... on the main
-    stream); ``fork``: the side streams wait for the main stream's work so far;
-    ``join``: the main stream waits for the side streams.  ``main=None``: one stream."""
-
-    def __init__(self, main, side):
-        self.main, self.side = main, side or []
-
-    def fork(self):
-        for s in self.side:
-            s.wait_stream(self.main)
-
-    def join(self):
-        for s in self.side:
-            self.main.wait_stream(s)
-
-    def __call__(self, i: int):
-        k = len(self.side) + 1
-        return torch.cuda.stream(self.side[i % k - 1]) if (self.side and i % k) else contextlib.nullcontext()
-
-
-class GPipeTrainer:
+class GPipeTrainer(CapturedStep):
     """Runs one stage of a GPipe schedule (``stage.forward/backward`` explicit API).
 
     On GPUs of one node the stage hand-off is the xGMI inbox kernels
@@ -222,7 +189,10 @@ class GPipeTrainer:
     with ``steps_per_graph``).  Otherwise (gloo CPU simulation, ``comm="rccl"``,
     or if the xGMI mapping fails) the hand-off is RCCL/gloo send/recv, eager."""
 
+    scope = "train_step_pp"
+
     def __init__(self, state: TrainState, mesh: Optional[Mesh], cfg: PipeConfig, act_dtype=torch.bfloat16):
+        CapturedStep.__init__(self)
         self.state, self.mesh, self.cfg = state, mesh, cfg
         self.model = state.apply_fn
         self.S = C.axis_size(mesh, cfg.pipe_axis)
@@ -239,9 +209,6 @@ class GPipeTrainer:
         self._mslab = (torch.zeros(1024, 4, dtype=torch.float32, device=self.dev)
                        if (self.dev.type == "cuda" and self.n_dp == 1
                            and os.environ.get("JDT_XENT_SLAB", "1") != "0") else None)
-        self.graph = None
-        self._ahead = None
-        self.multi = None
         self.p2p = None
         self._p2p_tried = False
         self.xg = None
@@ -249,6 +216,12 @@ class GPipeTrainer:
         self.wgrad = K.WGradStream(self.dev) if (self.dev.type == "cuda" and cfg.overlap_wgrad) else None
         self._mb_streams = None
         self._w_streams = None
+        self._comm_stream = None       # the overlapped data-axis sync's stream ...
+        self._buckets = None           # ... its buckets (_sync_buckets) ...
+        self._synced = False           # ... and whether this step's W pass already issued it
+        self._arena = None             # deferred weight-gradient buffers (_wgrad_arena)
+        self._eo = None                # in-epilogue AdamW: None = undecided, False = off
+        self._ov_opt = None            # side-stream AdamW, likewise
         self.stage_engine = None
         self._engine_tried = False
         self.deep_engine = None
@@ -314,10 +287,9 @@ class GPipeTrainer:
             return "none"
         if (self.S == 1 or self.p2p is not None or self.pp_kernel is not None) and (self.n_dp == 1 or self.xg is not None):
             return "xgmi"
-        from ..runtime.dist import backend
+        from ..runtime.dist import backend_name
 
-        b = backend()
-        return "rccl" if b == "nccl" else (b or "none")
+        return backend_name()
 
     @property
     def xgmi_status(self) -> str:
@@ -342,13 +314,10 @@ class GPipeTrainer:
         still writes into the old inboxes.  Never called inside a stream capture."""
         if not self._handoffs_stale:
             return
-        from ..runtime.dist import quiesce
+        from ..runtime.dist import quiesce_and_close
 
         self._handoffs_stale = False
-        quiesce(self.dev)
-        for r in (self.pp_kernel, self.p2p):
-            if r is not None:
-                r.close()
+        quiesce_and_close(self.dev, self.pp_kernel, self.p2p)
         self.pp_kernel = self.p2p = None
         self._pp_kernel_tried = self._p2p_tried = False
 
@@ -507,7 +476,7 @@ class GPipeTrainer:
         first parameter to the next group's (FlatParams offsets are 4-aligned, so every
         range is a valid kernel bucket); the range that ends the flat buffer also carries
         the metric slots, and the last bucket issued advances the optimizer step."""
-        if getattr(self, "_buckets", None) is None:
+        if self._buckets is None:
             P = self.state.params
             groups = self.model.sync_groups()
             starts = sorted((P.offsets[first][0], key) for key, first in groups)
@@ -528,9 +497,9 @@ class GPipeTrainer:
         tx, o = st.tx, st.opt_state
         scale = 1.0 / (cfg.num_microbatches * self.n_dp)
         main = torch.cuda.current_stream(self.dev)
-        cs = getattr(self, "_comm_stream", None)
-        if cs is None:
-            cs = self._comm_stream = torch.cuda.Stream(self.dev)
+        if self._comm_stream is None:
+            self._comm_stream = torch.cuda.Stream(self.dev)
+        cs = self._comm_stream
         G = P.grad
         gemms = {}
         for part in (["head"] if self.model.has_head else []) + list(self.model.layers):
@@ -569,9 +538,7 @@ class GPipeTrainer:
         arena = self._wgrad_arena(batch.size)
         if arena is None:
             return False
-        if self._mb_streams is None or len(self._mb_streams) != k - 1:
-            self._mb_streams = [torch.cuda.Stream(self.dev) for _ in range(k - 1)]
-        on = _MbStreams(torch.cuda.current_stream(self.dev), self._mb_streams)
+        on = self._on_streams(k)
         out, cache = self.model.forward(P, batch.inputs, train=True, seed=seed, offset=0, step=st.step_tensor,
                                         arena=arena, mb=0, n_mb=1)
         d = arena.head["dlog"] if self.model.has_head else torch.empty_like(out)
@@ -606,11 +573,13 @@ class GPipeTrainer:
         """Microbatch i's passes (and the W pass's GEMM j) run on stream i % k when
         ``cfg.mb_streams`` = k > 1 applies: GPU, one stage, deferred weight gradients."""
         k = self._mb_streams_k()
-        if not (k > 1 and arena is not None):
-            return _MbStreams(None, None)
-        if self._mb_streams is None or len(self._mb_streams) != k - 1:
-            self._mb_streams = [torch.cuda.Stream(self.dev) for _ in range(k - 1)]
-        return _MbStreams(torch.cuda.current_stream(self.dev), self._mb_streams)
+        return self._on_streams(k if arena is not None else 1)
+
+    def _on_streams(self, k: int) -> "_MbStreams":
+        """Work item i on stream i % k (the k - 1 side streams are kept across steps)."""
+        on = mb_streams(self._mb_streams, k, self.dev)
+        self._mb_streams = on.side or self._mb_streams
+        return on
 
     def _forward_mb(self, batch, P, st, seed, caches, dlogits, arena, akw, i, mb):
         n_mb = self.cfg.num_microbatches
@@ -634,12 +603,11 @@ class GPipeTrainer:
         for ``rows`` local sequences, or None (model without them, or defer_wgrad off)."""
         if not self.cfg.defer_wgrad or not hasattr(self.model, "weight_grads"):
             return None
-        ar = getattr(self, "_arena", None)
-        if ar is None or ar.nseq != rows:
+        if self._arena is None or self._arena.nseq != rows:
             from ..models.transformer import WGradArena
 
-            ar = self._arena = WGradArena(self.model, rows, self.dev)
-        return ar
+            self._arena = WGradArena(self.model, rows, self.dev)
+        return self._arena
 
     @property
     def single_stage_mode(self) -> str:
@@ -696,9 +664,7 @@ class GPipeTrainer:
     def invalidate(self):
         """After a checkpoint restore: drop captured graphs and the stage engine."""
         self._eo = None
-        self.graph = None
-        self._ahead = None
-        self.multi = None
+        self._drop_graphs()
         self.stage_engine = None
         self._engine_tried = False
         self.deep_engine = None
@@ -753,12 +719,7 @@ class GPipeTrainer:
         arrives while earlier ones still run (latency-bound ticks overlap instead of
         queueing), and the backward of one microbatch overlaps another's."""
         k = eng.n_sets
-        if k > 1:
-            if self._mb_streams is None or len(self._mb_streams) != k - 1:
-                self._mb_streams = [torch.cuda.Stream(self.dev) for _ in range(k - 1)]
-            on = _MbStreams(torch.cuda.current_stream(self.dev), self._mb_streams)
-        else:
-            on = _MbStreams(None, None)
+        on = self._on_streams(k)
         on.fork()
         for t in range(n_mb + self.S - 1):
             i = t - self.s
@@ -790,7 +751,7 @@ class GPipeTrainer:
         with no data axis on a GPU: weights updated in their final weight-gradient
         GEMMs, the rest by one multi-range launch in _sync_update.  JDT_LM_FUSED_OPT=0
         turns it off (A/B)."""
-        if getattr(self, "_eo", None) is None:
+        if self._eo is None:
             from ..utils.train_state import AdamW
 
             st, cfg = self.state, self.cfg
@@ -803,7 +764,7 @@ class GPipeTrainer:
 
     def _overlapped_opt(self):
         """The layer-by-layer side-stream AdamW (one GPU, one stage, no data axis)."""
-        if getattr(self, "_ov_opt", None) is None:
+        if self._ov_opt is None:
             from ..utils.train_state import AdamW
 
             st, cfg = self.state, self.cfg
@@ -820,11 +781,11 @@ class GPipeTrainer:
         st, P, cfg = self.state, self.state.params, self.cfg
         if self.pp_kernel is not None:
             return   # AdamW, the metrics fold and the step advance ran inside the stage launch
-        if getattr(self, "_synced", False):   # the W pass issued the sync per part (_overlapped_sync)
+        if self._synced:   # the W pass issued the sync per part (_overlapped_sync)
             self._synced = False
             return
         scale = 1.0 / (cfg.num_microbatches * self.n_dp)
-        ov = getattr(self, "_ov_opt", None)
+        ov = self._ov_opt
         if ov and ov.forked:   # AdamW already forked layer by layer during the backward
             ov.finish()
             with named_scope("sync_metrics"):
@@ -859,20 +820,13 @@ class GPipeTrainer:
         with named_scope("sync_metrics"):
             K.metrics_fold_(self.metrics, P.metrics_slot, slab=self._mslab)
 
-    def set_batch(self, batch: Batch):
-        """New data for captured graphs (see DataParallelTrainer.set_batch)."""
-        if getattr(self, "_static", None) is not None:
-            load_static_batch(self._static, batch, (self.deep_engine,))
+    @property
+    def _batch_engines(self):
+        return (self.deep_engine,)
 
-    def step(self, batch: Batch):
-        if self.graph is not None:
-            check_static_batch(getattr(self, "_static", None), batch)
-            with replay_scope("train_step_pp"):
-                self._ahead.replay(1) if getattr(self, "_ahead", None) else self.graph.replay()
-        else:
-            self._compute(batch)
-            self._sync_update()
-        self.state.step += 1
+    def _eager_step(self, batch: Batch):
+        self._compute(batch)
+        self._sync_update()
 
     # ------------------------------------------------------------------ hipGraph
     def capture(self, batch: Batch, steps_per_graph: int = 1):
@@ -880,50 +834,16 @@ class GPipeTrainer:
         Every rank of the mesh must capture; the batch must stay alive."""
         if not self.capturable:
             raise RuntimeError("pipeline step is not capturable (host-driven collectives)")
-        self._static = batch
         self._drop_stale_handoffs()   # a restore since the last step: rebuild outside the capture
 
-        def body():
-            self._compute(batch)
-            self._sync_update()
-
-        from .dp import capture_graph
-
-        g = capture_graph(body)
-        if g is None:   # a collective refused stream capture: the step stays eager
-            self.graph = None
-            return False
-        self.graph = g
         # one stage on the deep fused engine: layer 0's forward of the next step rides in
         # the layer-0 backward (run-ahead, fused_mlp.AheadGraphs: cold / primed graphs)
-        eng = self.deep_engine
-        self._ahead = None
-        if self.S == 1 and eng is not None and getattr(eng, "ahead_ok", False):
-            from .fused_mlp import AheadGraphs
+        def ahead():
+            ok = self.S == 1 and getattr(self.deep_engine, "ahead_ok", False)
+            return self.deep_engine if ok else None
 
-            self._ahead = AheadGraphs(eng, batch, steps_per_graph, pool=g.pool())
-            if steps_per_graph > 1:
-                self.multi = (steps_per_graph, self._ahead.graph(steps_per_graph))
-        elif steps_per_graph > 1:
-            gm = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(gm, pool=g.pool()):
-                for _ in range(steps_per_graph):
-                    body()
-            self.multi = (steps_per_graph, gm)
-        return True
-
-    def run_steps(self, batch: Batch, n: int):
-        if self.graph is not None:
-            check_static_batch(getattr(self, "_static", None), batch)
-        if self.graph is not None and self.multi is not None:
-            S, gm = self.multi
-            for _ in range(n // S):
-                with replay_scope("train_step_pp", S):
-                    self._ahead.replay(S) if self._ahead else gm.replay()
-            self.state.step += (n // S) * S
-            n %= S
-        for _ in range(n):
-            self.step(batch)
+        # (False: a collective refused stream capture, the step stays eager)
+        return self._capture(lambda: self._eager_step(batch), batch, steps_per_graph, ahead)
 
     def finalize(self):
         if self.deep_engine is not None:
@@ -940,14 +860,11 @@ class GPipeTrainer:
         """Release the inboxes and the xGMI context and drop the captured graphs, so
         another trainer can be built in this process (bench.py's autotune candidates).
         Collective (runtime.dist.quiesce)."""
-        from ..runtime.dist import quiesce
+        from ..runtime.dist import quiesce_and_close
 
-        quiesce(self.dev)
-        for r in (self.p2p, self.xg, self.pp_kernel):
-            if r is not None:
-                r.close()
+        quiesce_and_close(self.dev, self.p2p, self.xg, self.pp_kernel)
         self.p2p = self.xg = self.pp_kernel = None
-        self.graph = self._ahead = self.multi = None
+        self._drop_graphs()
 
     def loss_head(self, logits, labels, dlogits, n_parts: int = 1):
         """CE of ``labels`` (``n_parts`` merged microbatches: every row keeps its

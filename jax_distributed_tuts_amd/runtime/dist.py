@@ -108,6 +108,12 @@ def backend() -> Optional[str]:
     return dist.get_backend() if is_initialized() else None
 
 
+def backend_name() -> str:
+    """The process group's backend as the trainers report it (``comm_backend``)."""
+    b = backend()
+    return "rccl" if b == "nccl" else (b or "none")
+
+
 def shutdown():
     if is_initialized():
         try:
@@ -170,6 +176,15 @@ def quiesce(dev):
     if torch.device(dev).type == "cuda":
         torch.cuda.synchronize(dev)
     barrier()
+
+
+def quiesce_and_close(dev, *contexts):
+    """``quiesce``, then close every comm context of ``contexts`` that is not None (their
+    ``close`` is collective: every rank passes the same ones in the same order)."""
+    quiesce(dev)
+    for c in contexts:
+        if c is not None:
+            c.close()
 
 
 def barrier():

@@ -350,3 +350,66 @@ def unit_groups(out_dir):
     finally:
         dist.destroy_process_group()
     _save(out_dir, "unit", res)
+
+
+def ipc_context_lifecycle(out_dir):
+    """The IPC contexts' shared build / teardown protocol (comm/ipc_context.py) on a
+    fake context whose hooks touch no device: they record their calls and the unmap
+    hook drops ``unmapped.<rank>`` into the case's directory."""
+    import datetime
+    from ctypes import c_void_p
+
+    import torch.distributed as dist
+
+    from jax_distributed_tuts_amd.comm.ipc_context import HANDLE_BYTES, IpcContext
+
+    # a collective that does not pair up fails at this timeout instead of hanging
+    g = dist.new_group(timeout=datetime.timedelta(seconds=60))
+    r, W = D.rank(), D.world_size()
+
+    class Fake(IpcContext):
+        def __init__(self, case, fail_create=False):
+            super().__init__(g, r, W, torch.device("cpu"))
+            self.calls, self.dir = [], os.path.join(out_dir, case)
+            os.makedirs(self.dir, exist_ok=True)
+            self._finish(self._handshake(lambda h: self._create(fail_create), self._open, 2, "fake"))
+
+        def _create(self, fail):
+            self.calls.append("create")
+            self.ctx = c_void_p(1)
+            return -1 if fail else 0
+
+        def _open(self, all_handles):
+            self.calls.append("open")
+            assert len(all_handles) == W * 2 * HANDLE_BYTES
+            return 0
+
+        def _unmap(self):
+            self.calls.append("unmap")
+            open(os.path.join(self.dir, f"unmapped.{r}"), "w").close()
+
+        def _destroy(self):
+            if "unmap" in self.calls:   # two-phase: every rank has unmapped before any rank releases
+                assert all(os.path.exists(os.path.join(self.dir, f"unmapped.{q}")) for q in range(W))
+            self.calls.append("destroy")
+
+    def pairs():
+        t = torch.ones(1)
+        dist.all_reduce(t, group=g)
+        return float(t.item())
+
+    res = {}
+    a = Fake("a", fail_create=r == 1)    # (a) export failed on rank 1: closed again on every rank
+    res["a"] = {"ok": a.ok, "calls": a.calls, "ctx": bool(a.ctx), "sum": pairs()}
+    b = Fake("b")                        # (b) success, then the collective two-phase close
+    ok = b.ok
+    b.close()
+    res["b"] = {"ok": ok, "calls": list(b.calls), "closed": not b.ok and not b.ctx}
+    b.close()                            # (c) closing again is a no-op
+    res["c"] = {"calls": list(b.calls), "sum": pairs()}
+    d = Fake("d")                        # (d) rank 0 alone closes one-phase: no collective
+    if r == 0:
+        d.close(collective=False)
+    res["d"] = {"calls": list(d.calls), "sum": pairs()}
+    d.close(collective=False)
+    _save(out_dir, "ipcctx", res)

@@ -235,3 +235,17 @@ def test_single_stage_pipeline_merge_equals_reference(mode):
     for k, v in P.state_dict().items():
         _adam_close(v, ref_p[k], frac=5e-2)
     _metrics_close(tr.metrics, ref_m)
+
+
+def test_ipc_context_lifecycle(tmp_path):
+    """comm/ipc_context.py: a failed export closes the context on every rank, the
+    two-phase close releases nothing before every rank has unmapped, a second close is
+    a no-op, and the one-phase close issues no collective."""
+    spawn(W.ipc_context_lifecycle, 3, str(tmp_path))
+    for r, o in enumerate(_load(tmp_path, "ipcctx", 3)):
+        a, b, c, d = o["a"], o["b"], o["c"], o["d"]
+        assert a["ok"] is False and a["ctx"] is False and a["sum"] == 3.0
+        assert a["calls"] == ["create", "unmap", "destroy"]
+        assert b["ok"] is True and b["closed"] and b["calls"] == ["create", "open", "unmap", "destroy"]
+        assert c["calls"] == b["calls"] and c["sum"] == 3.0
+        assert d["calls"] == ["create", "open"] + (["destroy"] if r == 0 else []) and d["sum"] == 3.0

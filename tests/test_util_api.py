@@ -157,8 +157,9 @@ def test_stream_schedules_resolve_on_cpu(monkeypatch):
     from jax_distributed_tuts_amd.models.mlp import Classifier
     from jax_distributed_tuts_amd.models.transformer import TransformerConfig
     from jax_distributed_tuts_amd.parallel.dp import DataParallelTrainer, DPConfig, init_dp
-    from jax_distributed_tuts_amd.parallel.pipeline import PipeConfig, _MbStreams
+    from jax_distributed_tuts_amd.parallel.pipeline import PipeConfig
     from jax_distributed_tuts_amd.parallel.pipeline_lm import build_lm_pipeline
+    from jax_distributed_tuts_amd.parallel.step_program import _MbStreams
     from jax_distributed_tuts_amd.utils.train_state import adamw
 
     monkeypatch.delenv("JDT_MB_STREAMS", raising=False)

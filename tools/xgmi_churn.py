@@ -6,7 +6,7 @@ canary pattern that is checked after the next context's self-test and burst: a w
 through a stale peer mapping shows as a changed canary.  Teardown modes:
 
   two-phase  every rank closes its peer mappings, a barrier, then every rank releases
-             its own buffers (comm/xgmi.py close, the production path)
+             its own buffers (comm/ipc_context.py close, the production path)
   quiesce    every rank's queue drained, a barrier, then ONE call that closes this rank's
              mappings and releases its buffers (the round-5 teardown)
   none       the one-call teardown right after the last launch
