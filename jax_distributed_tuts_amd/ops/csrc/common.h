@@ -260,6 +260,15 @@ __device__ __forceinline__ void xcd_contiguous_tile(int& bx, int& by) {
   bx = t % gx; by = t / gx;
 }
 
+// The same for a 1-D grid of nwg workgroups, any nwg (the GEMM kernels): blocks b,
+// b + 8, ... share an XCD; this bijection gives each XCD a contiguous run of linear
+// tile ids (the first nwg % 8 XCDs one more), so neighbouring tiles, which share A
+// rows, land on the same XCD's L2 (cdna_hip_programming.md §5, T1).
+__device__ __forceinline__ int xcd_linear(int bid, int nwg) {
+  const int xcd = bid % 8, q = nwg / 8, rr = nwg % 8;
+  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + bid / 8;
+}
+
 // Run-ahead tile map, from the XCD the workgroup actually runs on (HW_REG_XCC_ID):
 // XCD x takes tiles [x G/8, (x+1) G/8) in chunk-fastest order, i.e. whole column
 // blocks (all gridDim.y input chunks of 16 hidden units: their Z1 partials meet in

@@ -187,6 +187,10 @@ struct Tile {
 
 __device__ __forceinline__ unsigned pack2(bf16_t lo, bf16_t hi) { return (unsigned)lo | ((unsigned)hi << 16); }
 
+// One MFMA sub-tile's accumulator: f32x4 for 16x16x32, f32x16 for 32x32x16.
+template <int MF>
+using acc_t = typename std::conditional<MF == 32, f32x16, f32x4>::type;
+
 // Load one 8-element chunk of a (rows x K) operand into packed bf16.
 //   non-transposed: elements (r, k0..k0+7) at base + r*ld + k
 //   transposed    : elements (r0..r0+7, k) at base + k*ld + r
@@ -834,18 +838,28 @@ __device__ __forceinline__ void gemm_finish_img(const GemmArgs& g, int tm0, int 
   }
 }
 
+// Host predicates shared by the launchers and planners below.
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// Split-K needs one BM x BN fp32 slab per (tile, slice) and one arrival ticket per
+// tile: do `tiles` tiles in `sp` slices still fit the workspace, after what earlier
+// problems of the same launch took (wsused floats, cntused tickets)?
+static bool slabs_fit(long tiles, int sp, int BM, int BN, long wsused, long cntused, const float* ws,
+                      const unsigned* counters, long ws_floats, long n_counters) {
+  return ws && counters && wsused + tiles * sp * BM * BN <= ws_floats && cntused + tiles <= n_counters;
+}
+
 // Host: gemm_finish_vec's 16-byte accesses need every row of C / Zout / Zin /
 // resid (and every batch / sub-batch slice) to start 16-byte aligned.
 static bool epi_vec_ok(const GemmArgs& g, int batch) {
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   auto rows = [&](const void* p, long ld, long s1, long s2, int f32) {
     if (!p) return true;
     const long q = f32 ? 4 : 8;
-    return al(p) && ld % q == 0 && (batch <= 1 || (s1 % q == 0 && (g.zin <= 1 || s2 % q == 0)));
+    return aligned16(p) && ld % q == 0 && (batch <= 1 || (s1 % q == 0 && (g.zin <= 1 || s2 % q == 0)));
   };
   return rows(g.C, g.ldc, g.sC, g.sC2, g.c_f32) && rows(g.Zout, g.ldz, g.sZ, 0, 0) && rows(g.Zin, g.ldzin, g.sZin, 0, 0) &&
-         rows(g.resid, g.ldr, g.sR, 0, 0) && (!g.bias || al(g.bias)) && g.N % 8 == 0 &&
-         (!g.opt_s || (al(g.opt_s) && al(g.opt_p) && al(g.opt_m) && al(g.opt_v) && g.ldc % 8 == 0));  // fused AdamW: 16-byte accesses
+         rows(g.resid, g.ldr, g.sR, 0, 0) && (!g.bias || aligned16(g.bias)) && g.N % 8 == 0 &&
+         (!g.opt_s || (aligned16(g.opt_s) && aligned16(g.opt_p) && aligned16(g.opt_m) && aligned16(g.opt_v) &&
+                       g.ldc % 8 == 0));  // fused AdamW: 16-byte accesses
 }
 
 template <int WM, int WN, int TM, int TN, int BK, bool AF32, bool BF32, int PRE, bool EXACT = false>
@@ -862,14 +876,7 @@ __global__ void __launch_bounds__(256) gemm_kernel(GemmArgs g, int tiles_n, int 
 #define AS(b) (smem + (b) * (BM + BN) * LDK)
 #define BS(b) (smem + (b) * (BM + BN) * LDK + BM * LDK)
 
-  // XCD-aware bijective remap: blocks b, b+8, ... share an XCD; give each XCD
-  // a contiguous run of tiles (cdna_hip_programming.md §5, T1).
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid % 8, q = nwg / 8, rr = nwg % 8;
-    bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + bid / 8;
-  }
+  const int bid = xcd_linear(blockIdx.x, gridDim.x);
   const int tm0 = (bid / tiles_n) * BM;
   const int tn0 = (bid % tiles_n) * BN;
   const int z = blockIdx.z;
@@ -1134,22 +1141,36 @@ __device__ __forceinline__ int tr_swz(int r) {
   else return ((r & 3) | (((r >> 3) & 1) << 2)) << 1;  // 128
 }
 
-template <int EXT>  // EXT = extent of the non-K dim of the tile (BM or BN)
+// One MFMA operand fragment from an LDS image.  EXT = extent of the non-K dim of the
+// tile (BM or BN); MF = the MFMA sub-tile, which only sets the lane mapping:
+//   MF = 16 (16x16x32): lane l holds row/column base + (l & 15), k = kk + 8 (l >> 4) + 0..7
+//   MF = 32 (32x32x16): lane l holds row/column base + (l & 31), k = kk + 8 (l >> 5) + 0..7
+template <int EXT, int MF = 16>
 __device__ __forceinline__ bf16x8 dma_frag(const bf16_t* img, bool kmajor_img, int base, int kk, int lane) {
   if (!kmajor_img) {
     // row image [EXT][64]: row r, 16-byte chunk c lives at slot c ^ (r & 7)
-    const int r = base + (lane & 15);
-    const int c = (kk >> 3) + (lane >> 4);
+    const int r = base + (lane & (MF - 1));
+    const int c = (kk >> 3) + (lane >> (MF == 32 ? 5 : 4));
     return *reinterpret_cast<const bf16x8*>(img + r * DMA_BK + ((c ^ (r & 7)) << 3));
   }
   // k-row image [64][EXT]: lane 4q+p of each 16-lane group addresses k-row q,
   // columns 4p..4p+3 of the group's 4-row block; it receives column (lane & 15).
+  // MF = 32: 16-lane group g gathers columns base + 16 (g & 1) .. +15 of k-rows
+  // kk + 8 (g >> 1) + 0..3 and + 4..7 (tr_swz ignores k bit 2, so both reads share
+  // one swizzled column).
   // Issued as inline asm: hipcc treats the ds_read_tr intrinsic as aliasing the
   // in-flight LDS-DMA and would wait vmcnt(0) before it, draining the ring.
   // The caller waits lgkmcnt(0) before the MFMAs read the fragments.
   typedef __attribute__((ext_vector_type(4))) short s4;
-  const int i16 = lane & 15, k1 = kk + 8 * (lane >> 4) + (i16 >> 2);
-  const int col = base + 4 * (i16 & 3);
+  const int i16 = lane & 15, g4 = lane >> 4;
+  int k1, col;
+  if constexpr (MF == 32) {
+    k1 = kk + 8 * (g4 >> 1) + (i16 >> 2);
+    col = base + 16 * (g4 & 1) + 4 * (i16 & 3);
+  } else {
+    k1 = kk + 8 * g4 + (i16 >> 2);
+    col = base + 4 * (i16 & 3);
+  }
   const int pcol = (((col >> 3) ^ tr_swz<EXT>(k1)) << 3) | (col & 7);
   const unsigned a0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) const bf16_t*)(img + k1 * EXT + pcol));
   s4 lo, hi;
@@ -1200,47 +1221,16 @@ __device__ __forceinline__ void stage_op(const bf16_t* src, long ld, int k0, bf1
     dma_stage<EXT, KMAJ, NW>(src, ld, k0, img, wid, lane);
   }
 }
-// 32x32x16 operand fragment (lane l: row/column base + (l & 31), k = kk + 8 (l >> 5) + 0..7)
-// from the same two images.  k-row image: each 16-lane group g gathers columns
-// base + 16 (g & 1) .. +15 of k-rows kk + 8 (g >> 1) + 0..3 and + 4..7 (two tr reads;
-// tr_swz ignores k bit 2, so both share one swizzled column).
-template <int EXT>
-__device__ __forceinline__ bf16x8 dma_frag32(const bf16_t* img, bool kmajor_img, int base, int kk, int lane) {
-  if (!kmajor_img) {
-    const int r = base + (lane & 31);
-    const int c = (kk >> 3) + (lane >> 5);
-    return *reinterpret_cast<const bf16x8*>(img + r * DMA_BK + ((c ^ (r & 7)) << 3));
-  }
-  typedef __attribute__((ext_vector_type(4))) short s4;
-  const int i16 = lane & 15, g4 = lane >> 4;
-  const int k1 = kk + 8 * (g4 >> 1) + (i16 >> 2);
-  const int col = base + 16 * (g4 & 1) + 4 * (i16 & 3);
-  const int pcol = (((col >> 3) ^ tr_swz<EXT>(k1)) << 3) | (col & 7);
-  const unsigned a0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) const bf16_t*)(img + k1 * EXT + pcol));
-  s4 lo, hi;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(a0));
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(a0), "n"(4 * EXT * 2));
-  bf16x8 f;
-  f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-  f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-  return f;
-}
-template <int EXT>
-__device__ __forceinline__ bf16x8 frag_op32(const bf16_t* img, bool kmajor_img, int base, int kk, int lane) {
-  if constexpr (EXT > 64) {
-    if (kmajor_img) return dma_frag32<64>(img + (base >> 6) * 64 * DMA_BK, true, base & 63, kk, lane);
-  }
-  return dma_frag32<EXT>(img, kmajor_img, base, kk, lane);
-}
-
-template <int EXT>
+// The fragment read matching stage_op's images (the 64-wide sub-image of a wide k-row operand).
+template <int EXT, int MF = 16>
 __device__ __forceinline__ bf16x8 frag_op(const bf16_t* img, bool kmajor_img, int base, int kk, int lane) {
   if constexpr (EXT > 64) {
-    if (kmajor_img) return dma_frag<64>(img + (base >> 6) * 64 * DMA_BK, true, base & 63, kk, lane);
+    if (kmajor_img) return dma_frag<64, MF>(img + (base >> 6) * 64 * DMA_BK, true, base & 63, kk, lane);
   }
-  return dma_frag<EXT>(img, kmajor_img, base, kk, lane);
+  return dma_frag<EXT, MF>(img, kmajor_img, base, kk, lane);
 }
 
+// stage_op with the operand's layout a runtime flag (the grouped kernel)
 template <int EXT>
 __device__ __forceinline__ void dma_stage_rt(bool kmaj, const bf16_t* src, long ld, int k0, bf16_t* img, int wid,
                                              int lane) {
@@ -1293,6 +1283,40 @@ __device__ __forceinline__ void dma_stage_tail(bool kmaj, const bf16_t* src, lon
   }
 }
 
+// One 64-deep K-tile of a wave's TM x TN grid of MF x MF sub-tiles, from the LDS images
+// As / Bs (AT / BT: the image is a k-row one, read transposed).
+// The transposed fragment reads are inline assembly (see dma_frag), which the compiler's
+// own s_waitcnt insertion does not track, so the wave waits for them itself before the
+// MFMAs; the empty asm then ties every fragment to that wait, so no MFMA can be scheduled
+// ahead of it.  Only two row images (plain ds_read_b128, tracked by the compiler) need no wait.
+template <int BM, int BN, int MF, bool AT, bool BT, class Acc, int TM, int TN>
+__device__ __forceinline__ void mma_ktile(const bf16_t* As, const bf16_t* Bs, Acc (&acc)[TM][TN], int wm, int wn,
+                                          int lane) {
+  static_assert(sizeof(Acc) == (MF == 32 ? 64 : 16), "accumulator of the MFMA sub-tile");
+#pragma unroll
+  for (int kk = 0; kk < DMA_BK; kk += (MF == 32 ? 16 : 32)) {
+    bf16x8 af[TM], bfr[TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) af[i] = frag_op<BM, MF>(As, AT, (wm * TM + i) * MF, kk, lane);
+#pragma unroll
+    for (int j = 0; j < TN; ++j) bfr[j] = frag_op<BN, MF>(Bs, BT, (wn * TN + j) * MF, kk, lane);
+    if constexpr (AT || BT) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(af[i]));
+#pragma unroll
+      for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(bfr[j]));
+    }
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        if constexpr (MF == 32) acc[i][j] = mfma32x32x16(af[i], bfr[j], acc[i][j]);
+        else acc[i][j] = mfma16x16x32(af[i], bfr[j], acc[i][j]);
+      }
+  }
+}
+
 // Wait until at most `pend` K-tiles (LPW LDS-DMA instructions each, per wave)
 // issued after the one about to be read are still in flight, then barrier.
 // P is the ring's maximum (S - 2); the count must be an immediate, hence the
@@ -1329,11 +1353,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_dma_kernel(GemmArgs g, int 
   static_assert((S - 2) * LPW <= 63, "vmcnt range");
   __shared__ __attribute__((aligned(16))) bf16_t smem[S * STAGE];
   const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid % 8, q = nwg / 8, rr = nwg % 8;
-    bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + bid / 8;
-  }
+  const int bid = xcd_linear(blockIdx.x, nwg);
   int tmi = bid / tiles_n, tni = bid % tiles_n;
   if (group_m > 1) {
     // row-groups of group_m tiles, column-major inside a group: an XCD's contiguous
@@ -1353,8 +1373,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_dma_kernel(GemmArgs g, int 
   const int kbeg = split * kchunk;
   const int nkt = (min(g.K, kbeg + kchunk) - kbeg) / (BK * R);  // host: kchunk % (64 R) == 0
 
-  using acc_t = typename std::conditional<MF == 32, f32x16, f32x4>::type;
-  acc_t acc[TM][TN];
+  acc_t<MF> acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1384,14 +1403,16 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_dma_kernel(GemmArgs g, int 
     for (int r = 0; r < R; ++r) {
       const bf16_t* As = smem + (kt % S) * STAGE + r * SUB;
       const bf16_t* Bs = As + BM * BK;
+      // mma_ktile's loop, written out: called through the helper, the fragment address arithmetic
+      // leaves the MFMAs' shadow (512-token dW GEMMs +4-5 %, BENCH_NOTES "GEMM de-duplication")
       if constexpr (MF == 32) {
 #pragma unroll
         for (int kk = 0; kk < BK; kk += 16) {
           bf16x8 af[TM], bfr[TN];
 #pragma unroll
-          for (int i = 0; i < TM; ++i) af[i] = frag_op32<BM>(As, AT, (wm * TM + i) * 32, kk, lane);
+          for (int i = 0; i < TM; ++i) af[i] = frag_op<BM, 32>(As, AT, (wm * TM + i) * 32, kk, lane);
 #pragma unroll
-          for (int j = 0; j < TN; ++j) bfr[j] = frag_op32<BN>(Bs, BT, (wn * TN + j) * 32, kk, lane);
+          for (int j = 0; j < TN; ++j) bfr[j] = frag_op<BN, 32>(Bs, BT, (wn * TN + j) * 32, kk, lane);
           if constexpr (AT || BT) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
@@ -1460,22 +1481,34 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_dma_kernel(GemmArgs g, int 
 // the second queueing behind the first's tail, and one launch gap is saved.
 // 32x32 tiles, no K split, K % 32 == 0 (a 32-deep tail tile is loaded with
 // EXEC-masked DMA); operand layouts are per-problem runtime flags.
-constexpr int GROUP_MAX = 4;
-struct GemmGroup {
-  GemmArgs g[GROUP_MAX];
-  int tiles_n[GROUP_MAX];
-  int start[GROUP_MAX + 1];
-  int n;
+//
+// The problem table of a multi-problem launch (this kernel and the W pass below):
+// problem p owns the linear workgroup ids [start[p], start[p + 1]), tile-major inside
+// a K-slice, slices outermost.
+template <int MAXP>
+struct GemmTable {
+  GemmArgs g[MAXP];
+  int tiles_n[MAXP];
+  int start[MAXP + 1];
+  int n;                  // problems
   // per-problem split-K (1 = none): a long-K problem (e.g. an input gradient
   // with K = d_ff next to its K = tokens weight gradient) would otherwise be the
   // group's long pole; its slices combine through gemm_finish's slabs/tickets
-  int splits[GROUP_MAX];
-  long wsoff[GROUP_MAX];
-  int cntoff[GROUP_MAX];
-  int vec[GROUP_MAX];   // epi_vec_ok per problem
+  int splits[MAXP];
+  long wsoff[MAXP];       // the problem's slabs / tickets inside ws / counters
+  int cntoff[MAXP];
   float* ws;
   unsigned* counters;
+  int total;              // workgroups
 };
+constexpr int GROUP_MAX = 4;
+struct GemmGroup : GemmTable<GROUP_MAX> {   // passed by value
+  int vec[GROUP_MAX];   // epi_vec_ok per problem
+};
+
+// Operand layouts are runtime flags here and the K loop has a uniform tail break, so this
+// kernel has its own K-tile loop (mma_ktile takes the layouts at compile time) and the
+// EXEC-masked dma_stage_tail.
 
 template <int S, bool TAIL, int TM = 1, int TN = 1>
 __global__ void __launch_bounds__(256) gemm_dma_group_kernel(GemmGroup G) {
@@ -1484,12 +1517,7 @@ __global__ void __launch_bounds__(256) gemm_dma_group_kernel(GemmGroup G) {
   constexpr int STAGE = (BM + BN) * BK;
   constexpr int LPW = BM / 32 + BN / 32;
   __shared__ __attribute__((aligned(16))) bf16_t smem[S * STAGE];
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid % 8, q = nwg / 8, rr = nwg % 8;
-    bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + bid / 8;
-  }
+  const int bid = xcd_linear(blockIdx.x, gridDim.x);
   int p = 0;
 #pragma unroll
   for (int t = 1; t < GROUP_MAX; ++t)
@@ -1547,7 +1575,7 @@ __global__ void __launch_bounds__(256) gemm_dma_group_kernel(GemmGroup G) {
       for (int j = 0; j < TN; ++j)
         bfr[j] = bt ? frag_op<BN>(Bs, true, (wn * TN + j) * 16, kk, lane)
                     : frag_op<BN>(Bs, false, (wn * TN + j) * 16, kk, lane);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // asm tr reads retired (see gemm_dma_kernel)
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // asm tr reads retired (see mma_ktile)
 #pragma unroll
       for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(af[i]));
 #pragma unroll
@@ -1586,17 +1614,7 @@ __global__ void __launch_bounds__(256) gemm_dma_group_kernel(GemmGroup G) {
 // stream's small GEMMs queueing behind its large ones, and the AdamW epilogues of one
 // problem overlap the main loops of the others.
 constexpr int WP_MAX = 40;
-struct GemmWTable {
-  int n, total;
-  int start[WP_MAX + 1];
-  int tiles_n[WP_MAX];
-  int splits[WP_MAX];
-  long wsoff[WP_MAX];
-  int cntoff[WP_MAX];
-  float* ws;
-  unsigned* counters;
-  GemmArgs g[WP_MAX];
-};
+struct GemmWTable : GemmTable<WP_MAX> {};   // lives in device memory
 
 template <int TM, int TN, int MF, int S>
 __global__ void __launch_bounds__(256) gemm_wpass_kernel(const GemmWTable* __restrict__ T) {
@@ -1606,13 +1624,7 @@ __global__ void __launch_bounds__(256) gemm_wpass_kernel(const GemmWTable* __res
   constexpr int LPW = (BM + BN) / (8 * NW);   // glds per wave per K-tile
   static_assert((S - 2) * LPW <= 63, "vmcnt range");
   __shared__ __attribute__((aligned(16))) bf16_t smem[S * STAGE];
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid % 8, q = nwg / 8, rr = nwg % 8;
-    bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + bid / 8;
-  }
-  // the problem: scalar loads of the prefix table (wave-uniform address)
+  const int bid = xcd_linear(blockIdx.x, gridDim.x);
   const int n = T->n;
   int p = 0;
   for (int t = 1; t < n; ++t)
@@ -1630,8 +1642,7 @@ __global__ void __launch_bounds__(256) gemm_wpass_kernel(const GemmWTable* __res
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
   const int nkt = kchunk / BK;
-  using acc_t = typename std::conditional<MF == 32, f32x16, f32x4>::type;
-  acc_t acc[TM][TN];
+  acc_t<MF> acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1651,44 +1662,7 @@ __global__ void __launch_bounds__(256) gemm_wpass_kernel(const GemmWTable* __res
     dma_wait_barrier<LPW, S - 2>(min(S - 2, nkt - 1 - kt));
     if (kt + S - 1 < nkt) issue(kt + S - 1);
     const bf16_t* As = smem + (kt % S) * STAGE;
-    const bf16_t* Bs = As + BM * BK;
-    if constexpr (MF == 32) {
-#pragma unroll
-      for (int kk = 0; kk < BK; kk += 16) {
-        bf16x8 af[TM], bfr[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = frag_op32<BM>(As, true, (wm * TM + i) * 32, kk, lane);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bfr[j] = frag_op32<BN>(Bs, true, (wn * TN + j) * 32, kk, lane);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // asm tr reads retired (gemm_dma_kernel)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(af[i]));
-#pragma unroll
-        for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(bfr[j]));
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = mfma32x32x16(af[i], bfr[j], acc[i][j]);
-      }
-    } else {
-#pragma unroll
-      for (int kk = 0; kk < BK; kk += 32) {
-        bf16x8 af[TM], bfr[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) af[i] = frag_op<BM>(As, true, (wm * TM + i) * 16, kk, lane);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) bfr[j] = frag_op<BN>(Bs, true, (wn * TN + j) * 16, kk, lane);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(af[i]));
-#pragma unroll
-        for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(bfr[j]));
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = mfma16x16x32(af[i], bfr[j], acc[i][j]);
-      }
-    }
+    mma_ktile<BM, BN, MF, true, true>(As, As + BM * BK, acc, wm, wn, lane);
   }
   __syncthreads();
   static_assert((BM * (BN + 4) + 4) * 4 <= S * STAGE * 2, "output image fits the staging ring");
@@ -1729,7 +1703,7 @@ static int launch_cfg(const GemmArgs& g, int batch, int splits, float* ws, long 
   const int ktiles = (g.K + BK - 1) / BK;
   // vector loads need 16-byte aligned rows: bf16 ld % 8, f32 ld % 4, aligned base
   auto vec_ok = [](const void* p, long ld, int f32) {
-    return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (f32 ? (ld % 4 == 0) : (ld % 8 == 0));
+    return aligned16(p) && (f32 ? (ld % 4 == 0) : (ld % 8 == 0));
   };
   const int va = vec_ok(g.A, g.lda, g.a_f32), vb = vec_ok(g.B, g.ldb, g.b_f32);
   const int vec = g_epi_vec && (long)g.M * g.N * batch >= g_epi_vec_min && epi_vec_ok(g, batch);
@@ -1743,7 +1717,7 @@ static int launch_cfg(const GemmArgs& g, int batch, int splits, float* ws, long 
     while (pre > 1 && ktiles % pre) pre >>= 1;
     if (g_exact_pre > 0 && g_exact_pre <= depth && ktiles % g_exact_pre == 0) pre = g_exact_pre;
     const int sp = ktiles / pre;
-    const bool ws_ok = sp == 1 || (ws && counters && tiles * sp * T::BM * T::BN <= ws_floats && tiles <= n_counters);
+    const bool ws_ok = sp == 1 || slabs_fit(tiles, sp, T::BM, T::BN, 0, 0, ws, counters, ws_floats, n_counters);
     // a K split pays a slab round trip + combine: only while the grid is not already full
     const bool split_ok = sp == 1 || g_exact_pre > 0 || tiles * sp <= 256;
     if (pre >= 2 && sp <= 16 && ws_ok && split_ok) {
@@ -1777,8 +1751,7 @@ static int launch_cfg(const GemmArgs& g, int batch, int splits, float* ws, long 
   }
   if (splits > ktiles) splits = ktiles;
   if (splits < 1) splits = 1;
-  if (splits > 1 && (!ws || !counters || tiles * splits * T::BM * T::BN > ws_floats || tiles > n_counters))
-    splits = 1;
+  if (splits > 1 && !slabs_fit(tiles, splits, T::BM, T::BN, 0, 0, ws, counters, ws_floats, n_counters)) splits = 1;
   const int kchunk = ((ktiles + splits - 1) / splits) * BK;
   splits = (g.K + kchunk - 1) / kchunk;
   dim3 grid(tiles_m * tiles_n, splits, batch);
@@ -1841,7 +1814,7 @@ static int launch_dma(const GemmArgs& g, int batch, int splits, float* ws, long 
     while (sp < 16 && tiles * sp < 512 && (g.K / (2 * sp)) % DMA_BK == 0 && g.K / (2 * sp) >= 8 * DMA_BK) sp *= 2;
   }
   if (sp < 1 || g.K % sp || (g.K / sp) % DMA_BK) return 1;
-  if (sp > 1 && (!ws || !counters || tiles * sp * BM * BN > ws_floats || tiles > n_counters)) sp = 1;
+  if (sp > 1 && !slabs_fit(tiles, sp, BM, BN, 0, 0, ws, counters, ws_floats, n_counters)) sp = 1;
   const int kchunk = g.K / sp;
   dim3 grid((g.M / BM) * tiles_n, sp, batch);
   const bool at = g.a_trans, bt = g.b_trans;
@@ -1924,8 +1897,7 @@ static bool g_gemm_tune = true;  // jdt_gemm_set_tune(0): heuristic only (A/B)
 static int gemm_dma(const GemmArgs& g, int batch, int cfg, int splits, float* ws, long ws_floats, unsigned* counters,
                     long n_counters, hipStream_t st) {
   if (g_gemm_no_dma || g.a_f32 || g.b_f32 || g.K % DMA_BK) return 1;
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  if (!al(g.A) || !al(g.B) || g.lda % 8 || g.ldb % 8) return 1;
+  if (!aligned16(g.A) || !aligned16(g.B) || g.lda % 8 || g.ldb % 8) return 1;
   if (batch > 1 && (g.sA % 8 || g.sB % 8 || g.sA2 % 8 || g.sB2 % 8)) return 1;
   int r_pref = 1, gm_pref = 0;
   if (cfg < 0 && g_gemm_tune && batch == 1 && splits < 0) {
@@ -1984,41 +1956,58 @@ static int gemm_dma(const GemmArgs& g, int batch, int cfg, int splits, float* ws
 // batch) -- the caller then launches the problems one by one.
 static int g_group_tile = 0;  // jdt_gemm_set_group_tile(t): force 32 / 64 / 128 tiles (sweeps); 0 = heuristic
 
-template <int T>
-static int group_plan(const GemmArgs* gs, int n, GemmGroup& G, float* ws, long ws_floats, unsigned* counters,
-                      long n_counters) {
-  G.n = n;
-  G.ws = ws;
-  G.counters = counters;
+// Lay out a multi-problem launch of BM x BN tiles (every M, N a multiple of them): the
+// problem table's prefix of workgroup ids and each problem's share of the split-K
+// workspace.  want_split(g, tiles) is the caller's split-K policy for one problem; a
+// split whose slabs or tickets no longer fit falls back to 1.  Returns the workgroup count.
+template <int MAXP, class SplitPolicy>
+static int table_layout(const GemmArgs* gs, int n, int BM, int BN, GemmTable<MAXP>& T, float* ws, long ws_floats,
+                        unsigned* counters, long n_counters, SplitPolicy want_split) {
+  T.n = n;
+  T.ws = ws;
+  T.counters = counters;
   int total = 0;
   long wsused = 0, cntused = 0;
   for (int p = 0; p < n; ++p) {
     const GemmArgs& g = gs[p];
+    const long tiles = (long)(g.M / BM) * (g.N / BN);
+    int sp = want_split(g, tiles);
+    if (sp > 1 && !slabs_fit(tiles, sp, BM, BN, wsused, cntused, ws, counters, ws_floats, n_counters)) sp = 1;
+    T.g[p] = g;
+    T.tiles_n[p] = g.N / BN;
+    T.start[p] = total;
+    T.splits[p] = sp;
+    T.wsoff[p] = wsused;
+    T.cntoff[p] = (int)cntused;
+    if (sp > 1) { wsused += tiles * sp * BM * BN; cntused += tiles; }
+    total += (int)(tiles * sp);
+  }
+  T.start[n] = total;
+  T.total = total;
+  return total;
+}
+
+template <int T>
+static int group_plan(const GemmArgs* gs, int n, GemmGroup& G, float* ws, long ws_floats, unsigned* counters,
+                      long n_counters) {
+  for (int p = 0; p < n; ++p) {
+    const GemmArgs& g = gs[p];
     if (g.M % T || g.N % T) return -1;
-    G.g[p] = g;
-    G.tiles_n[p] = g.N / T;
-    G.start[p] = total;
-    const long tiles = (long)(g.M / T) * (g.N / T);
-    // split long K into slices of >= 512 (8 K-tiles): measured on the transformer's
-    // dW + dX groups, where the K = d_ff input gradient otherwise runs 4x the
-    // K-steps of its neighbour (g_group_split = 0 disables, for A/B runs).  Big
-    // tiles split further while the problem has fewer tiles than CUs.
+    G.vec[p] = g_epi_vec && T * T >= 2048 && (long)g.M * g.N >= g_epi_vec_min && epi_vec_ok(g, 1);
+  }
+  // split long K into slices of >= 512 (8 K-tiles): measured on the transformer's
+  // dW + dX groups, where the K = d_ff input gradient otherwise runs 4x the
+  // K-steps of its neighbour (g_group_split = 0 disables, for A/B runs).  Big
+  // tiles split further while the problem has fewer tiles than CUs.
+  return table_layout(gs, n, T, T, G, ws, ws_floats, counters, n_counters, [&](const GemmArgs& g, long tiles) {
     int sp = 1;
     const int minslice = T >= 128 ? 4 : 8;
     if (g_group_split && ws && counters)
       while (sp < 8 && (g.K / (2 * sp)) % DMA_BK == 0 && g.K / (2 * sp) >= minslice * DMA_BK &&
              (T < 128 || tiles * sp < 256))
         sp *= 2;
-    if (sp > 1 && (wsused + tiles * sp * T * T > ws_floats || cntused + tiles > n_counters)) sp = 1;
-    G.splits[p] = sp;
-    G.wsoff[p] = wsused;
-    G.cntoff[p] = (int)cntused;
-    G.vec[p] = g_epi_vec && T * T >= 2048 && (long)g.M * g.N >= g_epi_vec_min && epi_vec_ok(g, 1);
-    if (sp > 1) { wsused += tiles * sp * T * T; cntused += tiles; }
-    total += (int)(tiles * sp);
-  }
-  G.start[n] = total;
-  return total;
+    return sp;
+  });
 }
 
 template <int TMN>
@@ -2046,9 +2035,8 @@ static int gemm_dma_group(const GemmArgs* gs, int n, float* ws, long ws_floats, 
   bool m64 = true, m128 = true;
   for (int p = 0; p < n; ++p) {
     const GemmArgs& g = gs[p];
-    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (g.a_f32 || g.b_f32 || g.K % 32 || g.K <= 0 || g.M % 32 || g.N % 32 || g.M <= 0 || g.N <= 0 || !al(g.A) ||
-        !al(g.B) || g.lda % 8 || g.ldb % 8 || g.zin > 1)
+    if (g.a_f32 || g.b_f32 || g.K % 32 || g.K <= 0 || g.M % 32 || g.N % 32 || g.M <= 0 || g.N <= 0 ||
+        !aligned16(g.A) || !aligned16(g.B) || g.lda % 8 || g.ldb % 8 || g.zin > 1)
       return 1;
     flops += 2L * g.M * g.N * g.K;
     m64 &= g.M % 64 == 0 && g.N % 64 == 0;
@@ -2108,12 +2096,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_ln_kernel(GemmArgs g, LnArg
   static_assert(LPW >= 1 && (S - 2) * LPW <= 63, "ring");
   static_assert((BM * (BN + 4) + 4) * 4 <= (AIMG + S * BSTAGE) * 2, "output image fits");
   __shared__ __attribute__((aligned(16))) bf16_t smem[AIMG + S * BSTAGE];
-  const int nwg = gridDim.x;
-  int bid = blockIdx.x;
-  {
-    const int xcd = bid % 8, q = nwg / 8, rr = nwg % 8;
-    bid = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + bid / 8;
-  }
+  const int bid = xcd_linear(blockIdx.x, gridDim.x);
   const int tmi = bid / tiles_n, tni = bid % tiles_n;
   const int tm0 = tmi * BM, tn0 = tni * BN;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -2199,25 +2182,7 @@ __global__ void __launch_bounds__(64 * WM * WN) gemm_ln_kernel(GemmArgs g, LnArg
     // writes are done (the wait's lgkmcnt(0) + barrier)
     dma_wait_barrier<LPW, S - 2>(min(S - 2, NKT - 1 - kt));
     if (kt + S - 1 < NKT) issue(kt + S - 1);
-    const bf16_t* As = smem + kt * (BM * BK);
-    const bf16_t* Bs = ring + (kt % S) * BSTAGE;
-#pragma unroll
-    for (int kk = 0; kk < BK; kk += 32) {
-      bf16x8 af[TM], bfr[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) af[i] = frag_op<BM>(As, false, (wm * TM + i) * 16, kk, lane);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) bfr[j] = frag_op<BN>(Bs, true, (wn * TN + j) * 16, kk, lane);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(af[i]));
-#pragma unroll
-      for (int j = 0; j < TN; ++j) asm volatile("" : "+v"(bfr[j]));
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma16x16x32(af[i], bfr[j], acc[i][j]);
-    }
+    mma_ktile<BM, BN, 16, false, true>(smem + kt * (BM * BK), ring + (kt % S) * BSTAGE, acc, wm, wn, lane);
   }
   __syncthreads();
   if (vec)
@@ -2296,10 +2261,9 @@ JDT_API int jdt_ln_args_size() { return (int)sizeof(LnArgs); }
 static int g_ln_cfg = 0;  // jdt_gemm_ln_set_cfg: force a tile (sweeps); 0 = heuristic
 // the fused kernel's tile config for (g, L), or -2: not eligible (LN + GEMM run apart)
 static int gemm_ln_cfg(const GemmArgs& g, const LnArgs& L) {
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   if (g.a_f32 || g.b_f32 || !g.b_trans || g.accumulate || g.Zin || g.zin > 1 || (g.K != 512 && g.K != 1024) ||
-      g.M % 32 || g.N % 64 || !al(L.X) || !al(L.Y) || !al(g.B) || L.ldx % 8 || L.ldy % 8 || g.ldb % 8 ||
-      !al(L.gamma) || !al(L.beta))
+      g.M % 32 || g.N % 64 || !aligned16(L.X) || !aligned16(L.Y) || !aligned16(g.B) || L.ldx % 8 || L.ldy % 8 ||
+      g.ldb % 8 || !aligned16(L.gamma) || !aligned16(L.beta))
     return -2;
   int cfg = g_ln_cfg;
   if (cfg <= 0) {
@@ -2354,40 +2318,20 @@ template <int BM, int BN>
 static int wpass_plan(const GemmArgs* gs, int n, GemmWTable* out, float* ws, long ws_floats, unsigned* counters,
                       long n_counters) {
   if (n <= 0 || n > WP_MAX) return -2;
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   long tiles_all = 0;
   for (int p = 0; p < n; ++p) {
     const GemmArgs& g = gs[p];
     if (!g.a_trans || !g.b_trans || g.a_f32 || g.b_f32 || !g.c_f32 || g.M % BM || g.N % BN || g.K % DMA_BK ||
-        !al(g.A) || !al(g.B) || g.lda % 8 || g.ldb % 8 || !epi_vec_ok(g, 1) || g.Zin || g.Zout || g.resid ||
-        g.keep_prob < 1.f)
+        !aligned16(g.A) || !aligned16(g.B) || g.lda % 8 || g.ldb % 8 || !epi_vec_ok(g, 1) || g.Zin || g.Zout ||
+        g.resid || g.keep_prob < 1.f)
       return -2;
     tiles_all += (long)(g.M / BM) * (g.N / BN);
   }
-  int total = 0;
-  long wsused = 0, cntused = 0;
-  out->n = n;
-  out->ws = ws;
-  out->counters = counters;
-  for (int p = 0; p < n; ++p) {
-    const GemmArgs& g = gs[p];
-    out->g[p] = g;
-    out->tiles_n[p] = g.N / BN;
-    out->start[p] = total;
-    const long tiles = (long)(g.M / BM) * (g.N / BN);
+  return table_layout(gs, n, BM, BN, *out, ws, ws_floats, counters, n_counters, [&](const GemmArgs& g, long) {
     int sp = 1;
     while (sp < 8 && tiles_all * sp < 512 && (g.K / (2 * sp)) % DMA_BK == 0 && g.K / (2 * sp) >= 8 * DMA_BK) sp *= 2;
-    if (sp > 1 && (!ws || !counters || wsused + tiles * sp * BM * BN > ws_floats || cntused + tiles > n_counters))
-      sp = 1;
-    out->splits[p] = sp;
-    out->wsoff[p] = wsused;
-    out->cntoff[p] = (int)cntused;
-    if (sp > 1) { wsused += tiles * sp * BM * BN; cntused += tiles; }
-    total += (int)(tiles * sp);
-  }
-  out->start[n] = total;
-  out->total = total;
-  return total;
+    return sp;
+  });
 }
 
 JDT_API int jdt_gemm_wpass_table_bytes() { return (int)sizeof(GemmWTable); }
