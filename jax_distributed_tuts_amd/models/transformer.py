@@ -209,6 +209,34 @@ class TransformerLM:
             h = logits
         return h, cache
 
+    # ------------------------------------------------------------------ decode
+    def decode_step(self, P: FlatParams, kv, x: torch.Tensor) -> torch.Tensor:
+        """One token per sequence through the blocks, in inference mode (no dropout, no
+        backward cache): ``x`` [B, d_model] bf16 is the embedded token at position
+        ``kv.pos`` (``ops.kernels.embed_decode``), ``kv`` a ``generation.KVCache``; returns
+        the logits [B, vocab] bf16.  The same ``ln_gemm`` / ``gemm`` calls as ``forward`` at
+        M = B, with ``attention_decode`` (appends to layer l's cache, attends over rows
+        0..pos) in the place of ``attention_fwd``.  ``kv.pos`` is only read."""
+        if not (self.has_embed and self.has_head):
+            raise ValueError("decode_step needs the full model (embedding and head): "
+                             "pipeline-split stages cannot generate")
+        c = self.cfg
+        h = x
+        for l in self.layers:
+            b = f"block_{l}"
+            qkv, _, _, _ = K.ln_gemm(h, P.p(f"{b}/ln1/scale"), P.p(f"{b}/ln1/bias"), P.s(f"{b}/attn/qkv/kernel"),
+                                     eps=c.ln_eps, bias=P.s(f"{b}/attn/qkv/bias"))
+            o = K.attention_decode(qkv, kv.k[l], kv.v[l], kv.pos, c.n_heads, out=kv.o)
+            x2 = K.gemm(o, P.s(f"{b}/attn/out/kernel"), bias=P.s(f"{b}/attn/out/bias"), resid=h)
+            # z_out as in forward: the GELU then sees the pre-activation rounded to bf16
+            z1 = torch.empty(x2.shape[0], c.d_ff, dtype=torch.bfloat16, device=x2.device)
+            u, _, _, _ = K.ln_gemm(x2, P.p(f"{b}/ln2/scale"), P.p(f"{b}/ln2/bias"), P.s(f"{b}/mlp/fc1/kernel"),
+                                   eps=c.ln_eps, bias=P.s(f"{b}/mlp/fc1/bias"), act="gelu", z_out=z1)
+            h = K.gemm(u, P.s(f"{b}/mlp/fc2/kernel"), bias=P.s(f"{b}/mlp/fc2/bias"), resid=x2)
+        logits, _, _, _ = K.ln_gemm(h, P.p("ln_f/scale"), P.p("ln_f/bias"), P.s("head/kernel"), eps=c.ln_eps,
+                                    bias=P.s("head/bias"))
+        return logits
+
     # ------------------------------------------------------------------ backward
     def backward(self, P: FlatParams, cache: _Cache, dout: torch.Tensor, *, dout_is_dz: bool = True,
                  need_dx: bool = False, on_ready=None, wgrad=None, opt=None, after=None) -> Optional[torch.Tensor]:

@@ -110,6 +110,15 @@ _SIGS = {
     "jdt_flash_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "jdt_flash_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                               c_int, c_int, c_float, c_int, c_void_p]),
+    # csrc/attn_decode.hip: (qkv, k_cache, v_cache, o, pos, B, H, Dh, S_max, scale, stream)
+    "jdt_attn_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                c_float, c_void_p]),
+    # (tokens, wte, wpe, out, pos, B, S_max, d, vocab, stream)
+    "jdt_embed_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                 c_void_p]),
+    # (logits, ld, B, V, temperature, seed, stream_id, tokens, S_max, pos, ticket, stream)
+    "jdt_sample": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_ulonglong, ctypes.c_uint, c_void_p, c_int,
+                           c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -1,0 +1,313 @@
+// Autoregressive decode kernels: one new token per sequence against a KV cache.
+//
+// The three launchers of a decode step share one device word, ``pos`` (int32[1]): the
+// number of tokens already in the cache == the index of the token being processed.
+// Every kernel READS it from memory, so a captured step replays with no host
+// bookkeeping (like the trainers' device step counter); jdt_sample, the last launch
+// of a step, advances it.  A position outside the cache makes every kernel a no-op.
+//
+// attn_decode:  single-query attention.  M = 1: latency / memory bound, no MFMA and no
+//               LDS staging -- each cached K / V row goes straight to VGPRs with one
+//               16-byte load per 8 lanes' slice and is read exactly once.
+// embed_decode: x[b] = wte[tokens[b, pos]] + wpe[pos]   (the bits embed_fwd_kernel stores)
+// sample:       argmax (temperature 0) or inverse-CDF sampling of softmax(logits / T)
+#include "common.h"
+
+#include <limits.h>
+
+namespace jdt {
+
+constexpr int AD_DH = 64;      // head dim (8 lanes x 8 bf16 = one 128-byte row)
+constexpr int AD_SMAX = 128;   // cache rows per head the kernel covers
+constexpr int AD_KPP = 32;     // keys per pass: 256 threads / 8 lanes per key
+constexpr int AD_NP = AD_SMAX / AD_KPP;
+
+__device__ __forceinline__ void unpack8(const u32x4& r, float (&x)[8]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    x[2 * j] = bf2f((bf16_t)(r[j] & 0xffff));
+    x[2 * j + 1] = bf2f((bf16_t)(r[j] >> 16));
+  }
+}
+
+// sum over the 8 lanes of an aligned lane octet (all lanes active): the first three
+// steps of wave_sum_dpp; every lane of the octet gets the same value
+__device__ __forceinline__ float oct_sum_dpp(float v) {
+  v += dpp_mov<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += dpp_mov<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += dpp_mov<0x141>(v);  // row_half_mirror
+  return v;
+}
+
+// One workgroup per (batch, head).  Thread t: key group g = t / 8 (keys g, g + 32, ...),
+// column slice c = t % 8 (8 bf16 = 16 bytes of the 64-wide row).  Order: the token's k / v
+// rows go to the cache at row pos (and are used from registers, not read back), scores
+// over keys 0..pos, fp32 softmax statistics, p = exp(s - max) rounded to bf16 before P.V and
+// the fp32 sum scaled by 1 / l at the end (the rounding points of the training forward,
+// attn128.hip), o stored as bf16.
+__global__ void __launch_bounds__(256) attn_decode_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
+                                                         bf16_t* __restrict__ vc, bf16_t* __restrict__ o,
+                                                         const int* __restrict__ pos_ptr, int H, int S_max,
+                                                         float scale) {
+  __shared__ float red_m[4], red_l[4], red_o[4][AD_DH];
+  const int pos = pos_ptr[0];
+  if (pos < 0 || pos >= S_max) return;   // past the end: nothing is written (uniform exit)
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = tid & 7, g = tid >> 3;
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const long d = (long)H * AD_DH;
+  const bf16_t* row = qkv + (long)b * 3 * d + h * AD_DH + c * 8;
+  const u32x4 qv = *reinterpret_cast<const u32x4*>(row);
+  const u32x4 kn = *reinterpret_cast<const u32x4*>(row + d);
+  const u32x4 vn = *reinterpret_cast<const u32x4*>(row + 2 * d);
+  bf16_t* Kh = kc + (long)bh * S_max * AD_DH + c * 8;
+  bf16_t* Vh = vc + (long)bh * S_max * AD_DH + c * 8;
+  // every load of the step is issued before the first use; rows past pos are never read
+  u32x4 kr[AD_NP], vr[AD_NP];
+#pragma unroll
+  for (int i = 0; i < AD_NP; ++i) {
+    const int j = g + AD_KPP * i;
+    if (j < pos) {
+      kr[i] = *reinterpret_cast<const u32x4*>(Kh + (long)j * AD_DH);
+      vr[i] = *reinterpret_cast<const u32x4*>(Vh + (long)j * AD_DH);
+    } else {
+      kr[i] = kn;   // j == pos: the token itself; j > pos: masked below
+      vr[i] = vn;
+    }
+  }
+  if (g == (pos & (AD_KPP - 1))) {
+    *reinterpret_cast<u32x4*>(Kh + (long)pos * AD_DH) = kn;
+    *reinterpret_cast<u32x4*>(Vh + (long)pos * AD_DH) = vn;
+  }
+  float qf[8];
+  unpack8(qv, qf);
+  float s[AD_NP], m = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < AD_NP; ++i) {
+    float kf[8], dot = 0.f;
+    unpack8(kr[i], kf);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dot += qf[e] * kf[e];
+    dot = oct_sum_dpp(dot);
+    s[i] = (g + AD_KPP * i <= pos) ? dot * scale : -INFINITY;
+    m = fmaxf(m, s[i]);
+  }
+  m = wave_max_dpp(m);
+  if (lane == 0) red_m[w] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));   // finite: key 0 is always valid
+  float l = 0.f;
+#pragma unroll
+  for (int i = 0; i < AD_NP; ++i) {
+    s[i] = (g + AD_KPP * i <= pos) ? __expf(s[i] - m) : 0.f;
+    l += s[i];
+  }
+  l = wave_sum_dpp(c == 0 ? l : 0.f);   // one lane per key
+  if (lane == 0) red_l[w] = l;
+  __syncthreads();
+  l = (red_l[0] + red_l[1]) + (red_l[2] + red_l[3]);
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < AD_NP; ++i) {
+    const float p = round_bf(s[i]);   // exp(s - m) as bf16; 1 / l goes on the fp32 sum, as in attn128.hip
+    float vf[8];
+    unpack8(vr[i], vf);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] += p * vf[e];
+  }
+  // the 8 key groups of a wave (lanes c, c + 8, ...), then the 4 waves through LDS
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float a = acc[e];
+    a += __shfl_xor(a, 8, WAVE);
+    a += __shfl_xor(a, 16, WAVE);
+    a += __shfl_xor(a, 32, WAVE);
+    if (lane < 8) red_o[w][lane * 8 + e] = a;
+  }
+  __syncthreads();
+  if (tid < AD_DH) {
+    const float inv = 1.f / l;
+    o[(long)b * d + h * AD_DH + tid] = f2bf(((red_o[0][tid] + red_o[1][tid]) + (red_o[2][tid] + red_o[3][tid])) * inv);
+  }
+}
+
+// one thread per 8 columns, as embed_fwd_kernel (same bf16x8_add -> same bits)
+__global__ void __launch_bounds__(256) embed_decode_kernel(const int* __restrict__ tokens,
+                                                          const bf16_t* __restrict__ wte,
+                                                          const bf16_t* __restrict__ wpe, bf16_t* __restrict__ out,
+                                                          const int* __restrict__ pos_ptr, int B, int S_max, int d,
+                                                          int vocab) {
+  const int pos = pos_ptr[0];
+  if (pos < 0 || pos >= S_max) return;
+  const int i = blockIdx.x * 256 + threadIdx.x, per_row = d / 8;
+  if (i >= B * per_row) return;
+  const int b = i / per_row, c = (i % per_row) * 8;
+  const int v = tokens[(long)b * S_max + pos];
+  if ((unsigned)v >= (unsigned)vocab) return;   // never read outside the table
+  const u32x4 a = *reinterpret_cast<const u32x4*>(wte + (long)v * d + c);
+  const u32x4 p = *reinterpret_cast<const u32x4*>(wpe + (long)pos * d + c);
+  *reinterpret_cast<u32x4*>(out + (long)b * d + c) = bf16x8_add(a, p);
+}
+
+// 8 logits from column i0 (a multiple of 8) of a row; columns >= V read as -inf
+__device__ __forceinline__ void logits8(const bf16_t* row, int i0, int V, bool vec, float (&x)[8]) {
+  if (vec) {   // V % 8 == 0 and a 16-byte aligned row: i0 < V covers all 8
+    unpack8(*reinterpret_cast<const u32x4*>(row + i0), x);
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) x[e] = i0 + e < V ? bf2f(row[i0 + e]) : -INFINITY;
+}
+
+// One workgroup per row; thread t owns the contiguous columns [t * per, (t + 1) * per).
+// temperature == 0: argmax, lowest index on ties.  Otherwise inverse-CDF sampling: weights
+// w_i = exp((x_i - max) / T) in fp32, a fixed-order prefix sum over the threads' chunk sums,
+// target = u * total with u = word 0 of philox4x32(seed, b, (pos << 32) | stream) as 24 bits;
+// the first thread whose inclusive prefix exceeds the target walks its chunk to the first
+// column whose running sum does.  The token goes to tokens[b, pos + 1]; the workgroup that
+// takes the last arrival ticket (optim.hip's scheme: every workgroup has read pos by then)
+// stores pos + 1 and re-arms the ticket.  pos + 1 >= S_max: nothing is written at all.
+__global__ void __launch_bounds__(256) sample_kernel(const bf16_t* __restrict__ logits, long ld, int V,
+                                                    float temperature, unsigned long long seed, unsigned stream_id,
+                                                    int* __restrict__ tokens, int S_max, int* pos_ptr,
+                                                    unsigned* ticket, int vec) {
+  __shared__ float s_mx[4], s_w[4];
+  __shared__ int s_am[4], s_own[4];
+  const int pos = pos_ptr[0];
+  if (pos < 0 || pos + 1 >= S_max) return;   // uniform over the grid: the ticket stays armed at 0
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, b = blockIdx.x;
+  const bf16_t* row = logits + (long)b * ld;
+  const int per = (((V + 255) / 256) + 7) & ~7;
+  const int beg = tid * per, end = min(beg + per, V);
+  float mx = -INFINITY;
+  int am = INT_MAX;
+  for (int i0 = beg; i0 < end; i0 += 8) {
+    float x[8];
+    logits8(row, i0, V, vec, x);
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (x[e] > mx) { mx = x[e]; am = i0 + e; }
+  }
+  const float wmx = wave_max_dpp(mx);
+  const int wam = wave_min_dpp(mx == wmx ? am : INT_MAX);
+  if (lane == 0) { s_mx[w] = wmx; s_am[w] = wam; }
+  __syncthreads();
+  const float gmx = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
+  int gam = INT_MAX;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (s_mx[k] == gmx) gam = min(gam, s_am[k]);
+  if (gam >= V) gam = 0;   // a row with no finite maximum
+  int* dst = tokens + (long)b * S_max + pos + 1;
+  if (temperature <= 0.f) {
+    if (tid == 0) *dst = gam;
+  } else {
+    const float inv_t = 1.f / temperature;
+    float tsum = 0.f;
+    for (int i0 = beg; i0 < end; i0 += 8) {
+      float x[8];
+      logits8(row, i0, V, vec, x);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) tsum += __expf((x[e] - gmx) * inv_t);
+    }
+    float inc = tsum;   // inclusive scan over the wave's threads
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+      const float t = __shfl_up(inc, o, WAVE);
+      if (lane >= o) inc += t;
+    }
+    const float prev = __shfl_up(inc, 1, WAVE);
+    if (lane == WAVE - 1) s_w[w] = inc;
+    __syncthreads();
+    float woff = 0.f, total = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (k == w) woff = total;
+      total += s_w[k];
+    }
+    const u32x4 r = philox4x32(seed, (uint64_t)b, ((uint64_t)(unsigned)pos << 32) | (uint64_t)stream_id);
+    const float target = (float)(r.x >> 8) * (1.0f / 16777216.0f) * total;
+    const int own = wave_min_dpp(woff + inc > target ? tid : INT_MAX);
+    if (lane == 0) s_own[w] = own;
+    __syncthreads();
+    const int owner = min(min(s_own[0], s_own[1]), min(s_own[2], s_own[3]));
+    if (owner == INT_MAX) {   // u * total rounded up to total
+      if (tid == 0) *dst = gam;
+    } else if (tid == owner) {
+      float run = woff + (lane > 0 ? prev : 0.f);
+      int pick = -1, last = -1;
+      for (int i0 = beg; i0 < end && pick < 0; i0 += 8) {
+        float x[8];
+        logits8(row, i0, V, vec, x);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float wt = __expf((x[e] - gmx) * inv_t);
+          run += wt;
+          if (wt > 0.f && pick < 0) {
+            last = i0 + e;
+            if (run > target) pick = i0 + e;
+          }
+        }
+      }
+      *dst = pick >= 0 ? pick : (last >= 0 ? last : gam);
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned t = atomicAdd(ticket, 1u);
+    if (t == gridDim.x - 1) {
+      pos_ptr[0] = pos + 1;
+      __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+}  // namespace jdt
+using namespace jdt;
+
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// qkv [B, 3*H*Dh] bf16 (q | k | v), caches [B, H, S_max, Dh] bf16, o [B, H*Dh] bf16, pos int32[1]
+JDT_API int jdt_attn_decode(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H,
+                            int Dh, int S_max, float scale, void* stream) {
+  if (Dh != AD_DH) return -3;
+  if (S_max < 1 || S_max > AD_SMAX) return -4;
+  if (B < 0 || H < 1) return -5;
+  if (!qkv || !k_cache || !v_cache || !o || !pos) return -2;
+  if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(attn_decode_kernel, dim3(B * H), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache),
+                     static_cast<bf16_t*>(o), pos, H, S_max, scale);
+  return HIP_LAUNCH_CHECK();
+}
+
+// out [B, d] bf16 = wte[tokens[b, pos]] + wpe[pos]; tokens int32 [B, S_max]; wpe has >= S_max rows
+JDT_API int jdt_embed_decode(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos, int B,
+                             int S_max, int d, int vocab, void* stream) {
+  if (d < 8 || d % 8) return -3;
+  if (S_max < 1 || vocab < 1 || B < 0) return -5;
+  if (!tokens || !wte || !wpe || !out || !pos) return -2;
+  if (misaligned16(wte) || misaligned16(wpe) || misaligned16(out)) return -6;
+  if (B == 0) return 0;
+  const long n = (long)B * (d / 8);
+  if (n > INT_MAX) return -5;
+  hipLaunchKernelGGL(embed_decode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), tokens, static_cast<const bf16_t*>(wte),
+                     static_cast<const bf16_t*>(wpe), static_cast<bf16_t*>(out), pos, B, S_max, d, vocab);
+  return HIP_LAUNCH_CHECK();
+}
+
+// logits [B, V] bf16 (row stride ld); tokens int32 [B, S_max]; pos int32[1]; ticket: a zeroed
+// uint32 the kernel leaves zero again
+JDT_API int jdt_sample(const void* logits, long ld, int B, int V, float temperature, unsigned long long seed,
+                       unsigned stream_id, int* tokens, int S_max, int* pos, unsigned* ticket, void* stream) {
+  if (V < 1 || ld < V || S_max < 1 || B < 0) return -5;
+  if (!(temperature >= 0.f)) return -7;
+  if (!logits || !tokens || !pos || !ticket) return -2;
+  if (B == 0) return 0;
+  const int vec = (V % 8 == 0) && (ld % 8 == 0) && !misaligned16(logits);
+  hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const bf16_t*>(logits), ld, V, temperature, seed, stream_id, tokens, S_max, pos,
+                     ticket, vec);
+  return HIP_LAUNCH_CHECK();
+}

@@ -1001,3 +1001,118 @@ def colsum_(x, out):
     rc = _lib.lib().jdt_colsum(_ptr(x), x.stride(0), x.shape[0], x.shape[1], _ptr(out), _lib.stream_ptr())
     _lib.check(rc, "jdt_colsum")
     return out
+
+
+# ----------------------------------------------------------------------------- decode (KV cache)
+# The launches of a decode step share ``pos`` (device int32[1]): the number of tokens already
+# in the cache == the index of the token being processed.  The kernels read it from memory
+# (csrc/attn_decode.hip), so a captured step replays without host bookkeeping; a position
+# outside the cache makes each of them a no-op.
+AD_HEAD_DIM, AD_MAX_ROWS = 64, 128   # envelope of jdt_attn_decode (csrc/attn_decode.hip AD_DH, AD_SMAX)
+_SAMPLE_TICKET: dict = {}
+
+
+def _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out):
+    """Composed torch path (any head dim / cache length, any device): reads ``pos`` on the host."""
+    B, d3 = qkv.shape
+    Dh = d3 // 3 // H
+    S_max = k_cache.shape[2]
+    p = int(pos.item())
+    if p < 0 or p >= S_max:
+        return out
+    q, k, v = qkv.view(B, 3, H, Dh).unbind(1)
+    k_cache[:, :, p] = k
+    v_cache[:, :, p] = v
+    Kc, Vc = _bf(k_cache[:, :, :p + 1].float()), _bf(v_cache[:, :, :p + 1].float())
+    s = torch.einsum("bhd,bhjd->bhj", _bf(q.float()), Kc) * (1.0 / (Dh ** 0.5))
+    pr = torch.softmax(s, dim=-1).to(torch.bfloat16).float()   # p rounded to bf16 before P.V, as attention_fwd
+    out.copy_(torch.einsum("bhj,bhjd->bhd", pr, Vc).reshape(B, H * Dh).to(torch.bfloat16))
+    return out
+
+
+def attention_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, H: int,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One query token per sequence against a KV cache.  ``qkv`` [B, 3*H*Dh] bf16 (the decode
+    step's QKV projection, q | k | v as in training), ``k_cache`` / ``v_cache`` [B, H, S_max, Dh]
+    bf16 (one layer), ``pos`` int32[1] -> o [B, H*Dh] bf16.  Appends the token's k / v rows at
+    row ``pos``, then attends over rows 0..pos (softmax statistics fp32, p rounded to bf16
+    before P.V, fp32 accumulate).  ``pos >= S_max``: nothing is written, ``out`` keeps its
+    contents.  GPU, Dh = 64 and S_max <= 128: csrc/attn_decode.hip; other GPU shapes run the
+    composed torch path (which syncs on ``pos``)."""
+    B, d3 = qkv.shape
+    d = d3 // 3
+    Dh = d // H
+    assert k_cache.shape == v_cache.shape and k_cache.shape[:2] == (B, H) and k_cache.shape[3] == Dh
+    assert pos.dtype == torch.int32 and pos.numel() == 1
+    S_max = k_cache.shape[2]
+    if out is None:
+        out = torch.zeros(B, d, dtype=torch.bfloat16, device=qkv.device)
+    if not _is_gpu(qkv) or Dh != AD_HEAD_DIM or S_max > AD_MAX_ROWS:
+        return _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out)
+    for t in (qkv, k_cache, v_cache, out):
+        assert t.is_contiguous() and t.dtype == torch.bfloat16
+    rc = _lib.lib().jdt_attn_decode(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos), B, H, Dh, S_max,
+                                    float(1.0 / (Dh ** 0.5)), _lib.stream_ptr())
+    _lib.check(rc, "jdt_attn_decode")
+    return out
+
+
+def embed_decode(tokens: torch.Tensor, wte: torch.Tensor, wpe: torch.Tensor, pos: torch.Tensor,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x[b] = wte[tokens[b, pos]] + wpe[pos] (bf16, the bits ``embed_fwd`` gives that row);
+    ``tokens`` int32 [B, S_max], ``pos`` int32[1].  ``pos >= S_max``: ``out`` keeps its contents."""
+    B, S_max = tokens.shape
+    d = wte.shape[1]
+    assert tokens.dtype == torch.int32 and pos.dtype == torch.int32 and wpe.shape[0] >= S_max and wpe.shape[1] == d
+    if out is None:
+        out = torch.zeros(B, d, dtype=torch.bfloat16, device=tokens.device)
+    if not _is_gpu(tokens):
+        p = int(pos.item())
+        if 0 <= p < S_max:
+            out.copy_((wte.float()[tokens[:, p].long()] + wpe.float()[p]).to(torch.bfloat16))
+        return out
+    for t in (tokens, wte, wpe, out):
+        assert t.is_contiguous()
+    assert wte.dtype == wpe.dtype == out.dtype == torch.bfloat16 and out.shape == (B, d)
+    rc = _lib.lib().jdt_embed_decode(_ptr(tokens), _ptr(wte), _ptr(wpe), _ptr(out), _ptr(pos), B, S_max, d,
+                                     int(wte.shape[0]), _lib.stream_ptr())
+    _lib.check(rc, "jdt_embed_decode")
+    return out
+
+
+def sample_tokens(logits: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor, *, temperature: float = 0.0,
+                  seed: int = 0, stream_id: int = 0) -> torch.Tensor:
+    """One token per row of ``logits`` [B, V] bf16 into ``tokens[:, pos + 1]`` (int32 [B, S_max]),
+    then ``pos += 1``.  ``temperature == 0``: argmax, lowest index on ties; otherwise inverse-CDF
+    sampling of softmax(logits / T) in fp32 with one uniform per row: word 0 of
+    philox4x32(seed, counter = row, offset = (pos << 32) | stream_id) (``philox_uniform``).
+    ``pos + 1 >= S_max``: no token is written and ``pos`` stays."""
+    B, V = logits.shape
+    S_max = tokens.shape[1]
+    assert tokens.dtype == torch.int32 and tokens.shape[0] == B and pos.dtype == torch.int32 and pos.numel() == 1
+    assert temperature >= 0.0 and 0 <= stream_id < 2 ** 32
+    seed = int(seed) & (2 ** 64 - 1)
+    if not _is_gpu(logits):
+        p = int(pos.item())
+        if p < 0 or p + 1 >= S_max:
+            return tokens
+        x = _bf(logits.float())
+        tok = x.argmax(-1)
+        if temperature > 0.0:
+            w = torch.exp((x - x.max(-1, keepdim=True).values) / float(temperature))
+            cum = torch.cumsum(w, -1)
+            u = torch.from_numpy(philox_uniform(seed, (p << 32) | int(stream_id), np.arange(B), 0)).float()
+            hit = cum > (u * cum[:, -1])[:, None]
+            tok = torch.where(hit.any(-1), hit.to(torch.uint8).argmax(-1), tok)   # first column past the target
+        tokens[:, p + 1] = tok.to(torch.int32)
+        pos.add_(1)
+        return tokens
+    assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and tokens.is_contiguous()
+    key = str(logits.device)
+    ticket = _SAMPLE_TICKET.get(key)
+    if ticket is None:   # the kernel leaves it zero again: one word serves every call on the device
+        ticket = _SAMPLE_TICKET[key] = torch.zeros(1, dtype=torch.int32, device=logits.device)
+    rc = _lib.lib().jdt_sample(_ptr(logits), logits.stride(0), B, V, float(temperature), seed, int(stream_id),
+                               _ptr(tokens), S_max, _ptr(pos), _ptr(ticket), _lib.stream_ptr())
+    _lib.check(rc, "jdt_sample")
+    return tokens

@@ -32,6 +32,12 @@ int jdt_adamw(float* p, float* g, float* m, float* v, void* shadow, long n, floa
 int jdt_sgd(float* p, float* g, float* buf, void* shadow, long n, float lr, float momentum, float wd,
             float grad_scale, int* step, unsigned* ticket, int zero_grad, void* stream);
 int jdt_colsum(const void* x, long ld, int M, int N, float* out, void* stream);
+int jdt_attn_decode(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H, int Dh,
+                    int S_max, float scale, void* stream);
+int jdt_embed_decode(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos, int B, int S_max,
+                     int d, int vocab, void* stream);
+int jdt_sample(const void* logits, long ld, int B, int V, float temperature, unsigned long long seed,
+               unsigned stream_id, int* tokens, int S_max, int* pos, unsigned* ticket, void* stream);
 }
 
 static int failures = 0;
@@ -73,6 +79,23 @@ int main() {
   EXPECT(jdt_sgd(nullptr, nullptr, nullptr, nullptr, 0, .1f, 0.f, 0.f, 1.f, nullptr, nullptr, 1, nullptr) == 0,
          "sgd n = 0 is a no-op");
   EXPECT(jdt_colsum(handles, 7, 4, 7, nullptr, nullptr) == -3, "colsum rejects N % 8");
+  // decode launchers (attn_decode.hip): the envelope is checked before anything is launched
+  alignas(16) unsigned char buf[64];
+  int* ip = reinterpret_cast<int*>(buf);
+  unsigned* up = reinterpret_cast<unsigned*>(buf);
+  EXPECT(jdt_attn_decode(buf, buf, buf, buf, ip, 1, 2, 32, 128, .125f, nullptr) == -3, "attn_decode rejects head dim 32");
+  EXPECT(jdt_attn_decode(buf, buf, buf, buf, ip, 1, 2, 64, 129, .125f, nullptr) == -4, "attn_decode rejects S_max > 128");
+  EXPECT(jdt_attn_decode(buf, buf, buf, buf, ip, 1, 2, 64, 0, .125f, nullptr) == -4, "attn_decode rejects S_max 0");
+  EXPECT(jdt_attn_decode(buf, nullptr, buf, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -2, "attn_decode rejects null");
+  EXPECT(jdt_attn_decode(buf + 4, buf, buf, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -6,
+         "attn_decode rejects a misaligned qkv");
+  EXPECT(jdt_attn_decode(buf, buf, buf, buf, ip, 0, 2, 64, 128, .125f, nullptr) == 0, "attn_decode B = 0 is a no-op");
+  EXPECT(jdt_embed_decode(ip, buf, buf, buf, ip, 1, 128, 60, 8, nullptr) == -3, "embed_decode rejects d % 8");
+  EXPECT(jdt_embed_decode(ip, buf, buf, buf, ip, 0, 128, 64, 8, nullptr) == 0, "embed_decode B = 0 is a no-op");
+  EXPECT(jdt_sample(buf, 8, 1, 0, 0.f, 0, 0, ip, 128, ip, up, nullptr) == -5, "sample rejects V = 0");
+  EXPECT(jdt_sample(buf, 8, 1, 8, -1.f, 0, 0, ip, 128, ip, up, nullptr) == -7, "sample rejects temperature < 0");
+  EXPECT(jdt_sample(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, ip, nullptr, nullptr) == -2, "sample rejects a null ticket");
+  EXPECT(jdt_sample(buf, 8, 0, 8, 1.f, 0, 0, ip, 128, ip, up, nullptr) == 0, "sample B = 0 is a no-op");
   std::printf("asan host check: %d failure(s)\n", failures);
   return failures ? 1 : 0;
 }

@@ -1,0 +1,97 @@
+"""Decode-step timing of KV-cache generation (jax_distributed_tuts_amd/generation.py) for the
+default TransformerConfig at B = 1 and B = 16: us per decode step and tokens/s, launched
+eagerly against one captured step replayed per token, plus the kernel-launcher calls per step.
+
+    python tools/bench_generate.py [--steps 100] [--temperature 0.0]
+
+Each figure: ``--steps`` decode steps after a 16-token prefill, timed with events around the
+whole loop (prefill excluded), median of 5 runs.
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from jax_distributed_tuts_amd.generation import Generator  # noqa: E402
+from jax_distributed_tuts_amd.models.transformer import TransformerConfig, TransformerLM  # noqa: E402
+from jax_distributed_tuts_amd.ops import _lib  # noqa: E402
+from jax_distributed_tuts_amd.utils.flat import FlatParams  # noqa: E402
+
+PROMPT = 16
+
+
+class _CountingLib:
+    """The kernel library with every launcher call counted (setters / planners / size queries are not)."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, {}
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if "_set_" in name or name.endswith(("_eligible", "_size", "_bytes", "_plan")):
+            return fn
+
+        def counted(*a):
+            self.calls[name] = self.calls.get(name, 0) + 1
+            return fn(*a)
+
+        return counted
+
+
+def launches_per_step(gen):
+    real = _lib.lib
+    proxy = _CountingLib(real())
+    _lib.lib = lambda: proxy
+    try:
+        gen.step()
+    finally:
+        _lib.lib = real
+    return proxy.calls
+
+
+def timed(run, reset, steps):
+    ts = []
+    for _ in range(5):
+        reset()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(steps):
+            run()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b) * 1e3 / steps)
+    return sorted(ts)[2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--temperature", type=float, default=0.0)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    cfg = TransformerConfig()
+    assert PROMPT + a.steps <= cfg.seq_len
+    model = TransformerLM(cfg)
+    P = FlatParams(model.param_specs(), device=dev).init_(0)
+    for B in (1, 16):
+        gen = Generator(model, P, B, dev)
+        prompt = torch.randint(0, cfg.vocab_size, (B, PROMPT), generator=torch.Generator().manual_seed(1))
+        prompt = prompt.to(torch.int32).to(dev)
+        gen.generate(prompt, 2, temperature=a.temperature, capture=True)   # warm-up + the step capture
+        graph = gen._graphs[(float(a.temperature), 0)][0]
+        reset = lambda: gen.prefill(prompt)  # noqa: E731
+        reset()
+        calls = launches_per_step(gen)
+        t_e = timed(gen.step, reset, a.steps)
+        line = (f"generate B={B:2d} T={a.temperature}: eager {t_e:7.1f} us/step ({B / t_e * 1e6:9.0f} tokens/s)")
+        if graph is not None:
+            t_g = timed(graph.replay, reset, a.steps)
+            line += f" | captured {t_g:7.1f} us/step ({B / t_g * 1e6:9.0f} tokens/s)"
+        print(line + f" | {sum(calls.values())} launcher calls/step: "
+              + ", ".join(f"{k[4:]} x{v}" for k, v in sorted(calls.items())), flush=True)
+
+
+if __name__ == "__main__":
+    main()
