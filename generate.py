@@ -5,11 +5,15 @@ one captured decode step replayed per token).
     python generate.py --prompt-len 16 --max-new-tokens 32            # untrained weights
     python generate.py --train-steps 200 --temperature 0.8 --seed 3   # train on lm_batch first
     python generate.py --restore ckpt_dir                             # weights of a checkpoint
+    python generate.py --batch 3 --prompt-lens 5,16,9 --temperature 0.8 --top-k 50 --top-p 0.9 --eos-id 7
 
 Runs the HIP kernels on a GPU and the torch reference paths on CPU tensors when none is
-present.  The prompt is the first ``--prompt-len`` tokens of ``lm_batch``'s sequences.
-Not covered: ragged prompts, top-k / top-p / beam search, sequences past ``seq_len``,
-multi-GPU or pipeline-split generation.
+present.  The prompt is the first ``--prompt-len`` tokens of ``lm_batch``'s sequences;
+``--prompt-lens`` gives every sequence its own length (ragged prompts), ``--top-k`` /
+``--top-p`` restrict the sampler and ``--eos-id`` ends a sequence at that token.  Each row is
+printed up to its own final length.
+Not covered: beam search, repetition penalties, sequences past ``seq_len``, multi-GPU or
+pipeline-split generation.
 """
 from __future__ import annotations
 
@@ -39,21 +43,30 @@ def main(args):
             tr.step(batch)
         if hasattr(tr, "finalize"):
             tr.finalize()
+    lens = None
+    if args.prompt_lens:
+        lens = torch.tensor([int(v) for v in args.prompt_lens.split(",")])
+        if lens.numel() != args.batch:
+            raise SystemExit(f"--prompt-lens needs one length per sequence ({args.batch}), got {lens.numel()}")
+        args.prompt_len = int(lens.max())
     prompt = data.inputs[:args.batch, :args.prompt_len].contiguous().to(dev)
     gen = Generator(tr.state.apply_fn, tr.state.params, args.batch, dev)
     sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
-    kw = dict(temperature=args.temperature, seed=args.seed, capture=not args.eager)
+    kw = dict(temperature=args.temperature, seed=args.seed, capture=not args.eager, prompt_lens=lens,
+              top_k=args.top_k, top_p=args.top_p, eos_id=args.eos_id)
     out = gen.generate(prompt, args.max_new_tokens, **kw)   # first call: allocations and the step capture
     sync()
     t0 = time.perf_counter()
     out = gen.generate(prompt, args.max_new_tokens, **kw)
     sync()
     dt = time.perf_counter() - t0
+    lengths = gen.lengths.cpu().tolist()
     for b, row in enumerate(out.cpu().tolist()):
-        print(f"[generate] seq {b}: {' '.join(str(t) for t in row)}")
-    n = args.batch * args.max_new_tokens
-    print(f"[generate] device={dev} batch={args.batch} prompt={args.prompt_len} new={args.max_new_tokens} "
-          f"temperature={args.temperature} {'eager' if args.eager or dev.type != 'cuda' else 'captured'}: "
+        print(f"[generate] seq {b}: {' '.join(str(t) for t in row[:lengths[b]])}")
+    n = sum(lengths) - (int(lens.sum()) if lens is not None else args.batch * args.prompt_len)   # new tokens
+    print(f"[generate] device={dev} batch={args.batch} prompt={args.prompt_lens or args.prompt_len} "
+          f"new={args.max_new_tokens} temperature={args.temperature} top_k={args.top_k} top_p={args.top_p} "
+          f"eos_id={args.eos_id} {'eager' if args.eager or dev.type != 'cuda' else 'captured'}: "
           f"{n / dt:.1f} tokens/s ({dt * 1e3:.2f} ms with the prefill)")
 
 
@@ -65,6 +78,11 @@ if __name__ == "__main__":
     ap.add_argument("--max-new-tokens", type=int, default=32)
     ap.add_argument("--temperature", type=float, default=0.0, help="0: greedy")
     ap.add_argument("--seed", type=int, default=0, help="sampling seed (Philox stream)")
+    ap.add_argument("--top-k", type=int, default=0, help="sample from the k largest logits only (0: off)")
+    ap.add_argument("--top-p", type=float, default=1.0, help="nucleus sampling mass in (0, 1] (1: off)")
+    ap.add_argument("--eos-id", type=int, default=None, help="a sequence that emits this token stops there")
+    ap.add_argument("--prompt-lens", default=None, metavar="L0,L1,...",
+                    help="one prompt length per sequence (ragged prompts); overrides --prompt-len")
     ap.add_argument("--model-seed", type=int, default=0, help="parameter initialisation seed")
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--eager", action="store_true", help="launch every decode step eagerly (no graph replay)")

@@ -14,9 +14,17 @@ copies rows < P of every layer's k / v into the cache and sets ``pos = P - 1``: 
 decode step re-processes the last prompt token (rewriting cache row P - 1 with its own
 k / v) and samples token P from it.
 
-Out of scope: ragged prompt lengths within a batch, top-k / top-p and beam search,
-sequences longer than ``seq_len`` (the learned positions end there), multi-GPU or
-pipeline-split generation, and head dims other than 64 on the HIP path.
+Ragged batches: ``prefill(prompt, prompt_lens)`` / ``generate(..., prompt_lens=, eos_id=)``
+switch the cache to its per-row state, ``pos_rows`` int32[B] and ``end`` int32[B] (one past
+the last token index a row may hold).  The same kernels then read ``pos[b]``; the sampler
+advances row b while ``pos[b] + 1 < end[b]`` and, for a drawn ``eos_id``, sets ``end[b]`` to
+the row's length, which finishes it: its later steps re-process the same token (the same
+bits) and sample nothing, so the captured step still replays without host bookkeeping.
+The sampler can also be restricted to the top-k / top-p set (``ops.kernels.sample_tokens``).
+
+Out of scope: beam search, repetition penalties, sequences longer than ``seq_len`` (the
+learned positions end there), multi-GPU or pipeline-split generation, paged or compacted
+caches, removing finished rows from the batch, and head dims other than 64 on the HIP path.
 """
 from __future__ import annotations
 
@@ -33,7 +41,9 @@ from .utils.flat import FlatParams
 class KVCache:
     """Per-layer K / V ``[B, H, seq_len, Dh]`` bf16, ``tokens`` int32 ``[B, seq_len]``, the
     device position word ``pos`` int32[1] and ``o``, the decode step's attention output
-    ``[B, d_model]`` bf16 (one buffer, reused layer after layer)."""
+    ``[B, d_model]`` bf16 (one buffer, reused layer after layer).  The per-row state is
+    ``pos_rows`` int32[B] and ``end`` int32[B] (one past the last token index a row may hold);
+    ``per_row`` says which position tensor is live (``live_pos``): ``pos`` by default."""
 
     def __init__(self, cfg: TransformerConfig, batch: int, device):
         H, Dh = cfg.n_heads, cfg.d_model // cfg.n_heads
@@ -42,8 +52,15 @@ class KVCache:
         self.v = [mk() for _ in range(cfg.n_layers)]
         self.tokens = torch.zeros(batch, cfg.seq_len, dtype=torch.int32, device=device)
         self.pos = torch.zeros(1, dtype=torch.int32, device=device)
+        self.pos_rows = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.end = torch.full((batch,), cfg.seq_len, dtype=torch.int32, device=device)
+        self.per_row = False
         # attention output of the layer in flight (a step past the end leaves it as it is)
         self.o = torch.zeros(batch, cfg.d_model, dtype=torch.bfloat16, device=device)
+
+    @property
+    def live_pos(self) -> torch.Tensor:
+        return self.pos_rows if self.per_row else self.pos
 
 
 class Generator:
@@ -58,48 +75,82 @@ class Generator:
         self.kv = KVCache(model.cfg, self.batch, self.device)
         self.x = torch.zeros(self.batch, model.cfg.d_model, dtype=torch.bfloat16, device=self.device)
         self.temperature, self.seed = 0.0, 0
+        self.top_k, self.top_p, self.eos_id = 0, 1.0, -1
         self.logits: Optional[torch.Tensor] = None   # the last step's logits [B, vocab]
-        self._graphs: dict = {}                      # (temperature, seed) -> (graph, its logits)
+        self.lengths: Optional[torch.Tensor] = None  # int32 [B]: the final lengths of the last generate
+        # (temperature, seed) -> (graph, its logits); any other sampler setting or the
+        # per-row mode: (temperature, seed, top_k, top_p, eos_id, per_row)
+        self._graphs: dict = {}
 
     # ------------------------------------------------------------------ prefill
-    def prefill(self, prompt: torch.Tensor):
-        """``prompt`` int [B, P], 1 <= P <= seq_len: fills cache rows < P and sets pos = P - 1."""
+    def prefill(self, prompt: torch.Tensor, prompt_lens: Optional[torch.Tensor] = None):
+        """``prompt`` int [B, P], 1 <= P <= seq_len: fills cache rows < P and sets pos = P - 1.
+
+        ``prompt_lens`` (int [B], each in 1..P): ``prompt`` is right-padded, tokens at or past
+        a row's length are ignored, and the per-row state becomes live: ``pos_rows[b] =
+        len_b - 1``, ``end[b] = seq_len``.  Cache rows >= len_b of row b are never read before
+        the decode step writes them."""
         c = self.model.cfg
         if prompt.dim() != 2 or prompt.shape[0] != self.batch or not 1 <= prompt.shape[1] <= c.seq_len:
             raise ValueError(f"prompt must be [{self.batch}, 1..{c.seq_len}], got {tuple(prompt.shape)}")
+        B, Pn, H, Dh = self.batch, prompt.shape[1], c.n_heads, c.d_model // c.n_heads
+        prompt = prompt.to(device=self.device, dtype=torch.int32)
+        lens = None
+        if prompt_lens is not None:
+            lens = torch.as_tensor(prompt_lens).to(device=self.device)
+            if lens.shape != (B,) or lens.dtype.is_floating_point or int(lens.min()) < 1 or int(lens.max()) > Pn:
+                raise ValueError(f"prompt_lens must be {B} integers in 1..{Pn}, got {lens.tolist()}")
+            lens = lens.to(torch.int32)
+            prompt = prompt * (torch.arange(Pn, device=self.device)[None] < lens[:, None])   # padding -> token 0
         if int(prompt.min()) < 0 or int(prompt.max()) >= c.vocab_size:
             raise ValueError(f"prompt token outside [0, {c.vocab_size})")
-        B, Pn, H, Dh = self.batch, prompt.shape[1], c.n_heads, c.d_model // c.n_heads
         kv = self.kv
         kv.tokens.zero_()
-        kv.tokens[:, :Pn] = prompt.to(device=self.device, dtype=torch.int32)
+        kv.tokens[:, :Pn] = prompt
         _, cache = self.model.forward(self.P, kv.tokens)
         for l, bc in zip(self.model.layers, cache.blocks):
             qkv = bc.qkv.view(B, c.seq_len, 3, H, Dh)
             kv.k[l][:, :, :Pn] = qkv[:, :Pn, 1].permute(0, 2, 1, 3)
             kv.v[l][:, :, :Pn] = qkv[:, :Pn, 2].permute(0, 2, 1, 3)
-        kv.pos.fill_(Pn - 1)
+        kv.per_row = lens is not None
+        if kv.per_row:
+            kv.pos_rows.copy_(lens - 1)
+            kv.end.fill_(c.seq_len)
+        else:
+            kv.pos.fill_(Pn - 1)
 
     # ------------------------------------------------------------------ one step
     def step(self, sample: bool = True) -> torch.Tensor:
         """One decode step at position ``pos``; returns its logits [B, vocab].  ``sample``:
-        the sampler writes ``tokens[:, pos + 1]`` and advances ``pos`` (temperature / seed:
-        the attributes of that name).  ``sample=False`` (teacher forcing): ``tokens`` is left
-        alone and ``pos`` advances by a torch op."""
+        the sampler writes ``tokens[:, pos + 1]`` and advances ``pos`` (temperature / seed /
+        top_k / top_p / eos_id: the attributes of that name).  ``sample=False`` (teacher
+        forcing): ``tokens`` is left alone and ``pos`` advances by a torch op.  Per-row mode:
+        ``pos`` is ``kv.pos_rows``, and a row at its ``end`` neither samples nor advances."""
         kv, P = self.kv, self.P
-        K.embed_decode(kv.tokens, P.s("embed/wte"), P.s("embed/wpe"), kv.pos, out=self.x)
+        pos = kv.live_pos
+        K.embed_decode(kv.tokens, P.s("embed/wte"), P.s("embed/wpe"), pos, out=self.x)
         self.logits = self.model.decode_step(P, kv, self.x)
-        if sample:
-            K.sample_tokens(self.logits, kv.tokens, kv.pos, temperature=self.temperature, seed=self.seed)
+        if not sample:
+            pos.add_(1)
+        elif kv.per_row:
+            K.sample_tokens(self.logits, kv.tokens, pos, temperature=self.temperature, seed=self.seed, end=kv.end,
+                            eos_id=self.eos_id, top_k=self.top_k, top_p=self.top_p)
         else:
-            kv.pos.add_(1)
+            K.sample_tokens(self.logits, kv.tokens, pos, temperature=self.temperature, seed=self.seed,
+                            top_k=self.top_k, top_p=self.top_p)
         return self.logits
+
+    def _graph_key(self):
+        key = (self.temperature, self.seed)
+        if self.kv.per_row or self.top_k != 0 or self.top_p != 1.0 or self.eos_id >= 0:
+            key += (self.top_k, self.top_p, self.eos_id, self.kv.per_row)
+        return key
 
     def _replay(self):
         """The sampling step as a graph replay (captured on first use per sampler setting;
         one stream, no parallel branches).  The eager step before the capture is a real
         step: it also creates every lazily allocated workspace outside the capture."""
-        key = (self.temperature, self.seed)
+        key = self._graph_key()
         ent = self._graphs.get(key)
         if ent is None:
             eager = self.step()
@@ -117,22 +168,57 @@ class Generator:
 
     # ------------------------------------------------------------------ generate
     def generate(self, prompt: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, seed: int = 0,
-                 capture: bool = True) -> torch.Tensor:
+                 capture: bool = True, *, prompt_lens: Optional[torch.Tensor] = None, top_k: int = 0,
+                 top_p: float = 1.0, eos_id: Optional[int] = None, pad_id: int = 0) -> torch.Tensor:
         """``prompt`` int [B, P] -> int32 [B, P + max_new_tokens] (the prompt, then the new
         tokens).  ``temperature == 0``: greedy; otherwise softmax(logits / T) sampling from
-        Philox stream ``seed``.  ``capture`` (GPU only): the decode step is captured into a
-        graph once and replayed per token."""
+        Philox stream ``seed``, restricted to the ``top_k`` largest logits (0: off) and, of
+        those, the smallest head of probability mass >= ``top_p`` (1.0: off); ties at a
+        threshold are kept.  ``capture`` (GPU only): the decode step is captured into a graph
+        once per sampler setting and replayed per token.
+
+        ``prompt_lens`` (int [B], each in 1..P; ``prompt`` right-padded) or ``eos_id`` select the
+        per-row mode: row b starts at its own length len_b and may grow to len_b +
+        max_new_tokens; a row that emits ``eos_id`` stops there (the EOS is its last token)
+        while the others go on, and the loop ends early once every row has finished (checked
+        every 16 steps).  Returns int32 [B, max(len) + max_new_tokens] with ``pad_id`` at and
+        past each row's final length; ``self.lengths`` (int32 [B]) holds those lengths."""
         c = self.model.cfg
         Pn = prompt.shape[1] if prompt.dim() == 2 else 0
-        if max_new_tokens < 0 or Pn + max_new_tokens > c.seq_len:
-            raise ValueError(f"prompt length {Pn} + max_new_tokens {max_new_tokens} exceeds seq_len {c.seq_len} "
-                             "(the learned positions end there)")
-        self.prefill(prompt)
+        if top_k < 0 or not 0.0 < top_p <= 1.0:
+            raise ValueError(f"top_k must be >= 0 and top_p in (0, 1], got top_k={top_k} top_p={top_p}")
         self.temperature, self.seed = float(temperature), int(seed)
+        self.top_k, self.top_p = int(top_k), float(top_p)
+        self.eos_id = -1 if eos_id is None else int(eos_id)
         graph = capture and self.device.type == "cuda"
-        for _ in range(max_new_tokens):
-            if graph:
-                self._replay()
-            else:
-                self.step()
-        return self.kv.tokens[:, :Pn + max_new_tokens].clone()
+        run = self._replay if graph else self.step
+        if prompt_lens is None and eos_id is None:
+            if max_new_tokens < 0 or Pn + max_new_tokens > c.seq_len:
+                raise ValueError(f"prompt length {Pn} + max_new_tokens {max_new_tokens} exceeds seq_len "
+                                 f"{c.seq_len} (the learned positions end there)")
+            self.prefill(prompt)
+            for _ in range(max_new_tokens):
+                run()
+            self.lengths = torch.full((self.batch,), Pn + max_new_tokens, dtype=torch.int32, device=self.device)
+            return self.kv.tokens[:, :Pn + max_new_tokens].clone()
+        if self.eos_id >= c.vocab_size or (eos_id is not None and self.eos_id < 0):
+            raise ValueError(f"eos_id {eos_id} outside [0, {c.vocab_size})")
+        if prompt_lens is None:
+            prompt_lens = torch.full((self.batch,), Pn, dtype=torch.int32)
+        lens = torch.as_tensor(prompt_lens)
+        longest = int(lens.max()) if lens.numel() else 0
+        if max_new_tokens < 0 or longest + max_new_tokens > c.seq_len:
+            raise ValueError(f"longest prompt {longest} + max_new_tokens {max_new_tokens} exceeds seq_len "
+                             f"{c.seq_len} (the learned positions end there)")
+        self.prefill(prompt, lens)
+        kv = self.kv
+        kv.end.copy_(kv.pos_rows + 1 + max_new_tokens)
+        for i in range(1, max_new_tokens + 1):
+            run()
+            # a host read serialises the replay loop: look only every 16 steps
+            if self.eos_id >= 0 and i % 16 == 0 and i < max_new_tokens and bool((kv.pos_rows + 1 >= kv.end).all()):
+                break
+        self.lengths = kv.pos_rows + 1
+        out = kv.tokens[:, :longest + max_new_tokens].clone()
+        out[torch.arange(out.shape[1], device=self.device)[None] >= self.lengths[:, None]] = pad_id
+        return out

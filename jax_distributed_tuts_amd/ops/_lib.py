@@ -119,6 +119,17 @@ _SIGS = {
     # (logits, ld, B, V, temperature, seed, stream_id, tokens, S_max, pos, ticket, stream)
     "jdt_sample": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_ulonglong, ctypes.c_uint, c_void_p, c_int,
                            c_void_p, c_void_p, c_void_p]),
+    # per-row positions (pos int32[B]): the signatures of jdt_attn_decode / jdt_embed_decode
+    "jdt_attn_decode_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                     c_float, c_void_p]),
+    "jdt_embed_decode_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                      c_void_p]),
+    # (logits, ld, B, V, temperature, seed, stream_id, tokens, S_max, pos, ticket, top_k, top_p, stream)
+    "jdt_sample_filtered": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_ulonglong, ctypes.c_uint, c_void_p,
+                                    c_int, c_void_p, c_void_p, c_int, c_float, c_void_p]),
+    # (logits, ld, B, V, temperature, seed, stream_id, tokens, S_max, pos, end, eos_id, top_k, top_p, stream)
+    "jdt_sample_rows": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_ulonglong, ctypes.c_uint, c_void_p, c_int,
+                                c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
 }
 
 

@@ -6,11 +6,21 @@
 // bookkeeping (like the trainers' device step counter); jdt_sample, the last launch
 // of a step, advances it.  A position outside the cache makes every kernel a no-op.
 //
+// Per-row variants (the ``_rows`` launchers, the same kernel bodies with ROWS = true): the
+// state is one word per sequence, ``pos`` int32[B], plus ``end`` int32[B], one past the last
+// token index row b may hold.  Workgroup (b, ...) reads pos[b]; a row out of range is a
+// no-op for its own workgroups only.  jdt_sample_rows writes tokens[b, pos[b] + 1] and
+// advances pos[b] while pos[b] + 1 < min(end[b], S_max); a written token equal to
+// ``eos_id`` sets end[b] = pos[b] + 2, which finishes the row: later steps re-process the
+// token at the frozen pos[b] (the same bits again) and the sampler skips the row.
+// For a row whose position equals the shared one both variants give the same bits.
+//
 // attn_decode:  single-query attention.  M = 1: latency / memory bound, no MFMA and no
 //               LDS staging -- each cached K / V row goes straight to VGPRs with one
 //               16-byte load per 8 lanes' slice and is read exactly once.
 // embed_decode: x[b] = wte[tokens[b, pos]] + wpe[pos]   (the bits embed_fwd_kernel stores)
-// sample:       argmax (temperature 0) or inverse-CDF sampling of softmax(logits / T)
+// sample:       argmax (temperature 0) or inverse-CDF sampling of softmax(logits / T),
+//               optionally restricted to the top-k / top-p set (FILT = true)
 #include "common.h"
 
 #include <limits.h>
@@ -45,15 +55,16 @@ __device__ __forceinline__ float oct_sum_dpp(float v) {
 // over keys 0..pos, fp32 softmax statistics, p = exp(s - max) rounded to bf16 before P.V and
 // the fp32 sum scaled by 1 / l at the end (the rounding points of the training forward,
 // attn128.hip), o stored as bf16.
+template <bool ROWS>
 __global__ void __launch_bounds__(256) attn_decode_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
                                                          bf16_t* __restrict__ vc, bf16_t* __restrict__ o,
                                                          const int* __restrict__ pos_ptr, int H, int S_max,
                                                          float scale) {
   __shared__ float red_m[4], red_l[4], red_o[4][AD_DH];
-  const int pos = pos_ptr[0];
-  if (pos < 0 || pos >= S_max) return;   // past the end: nothing is written (uniform exit)
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = tid & 7, g = tid >> 3;
   const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const int pos = pos_ptr[ROWS ? b : 0];
+  if (pos < 0 || pos >= S_max) return;   // past the end: nothing is written (uniform over the workgroup)
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = tid & 7, g = tid >> 3;
   const long d = (long)H * AD_DH;
   const bf16_t* row = qkv + (long)b * 3 * d + h * AD_DH + c * 8;
   const u32x4 qv = *reinterpret_cast<const u32x4*>(row);
@@ -131,16 +142,17 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const bf16_t* __restri
 }
 
 // one thread per 8 columns, as embed_fwd_kernel (same bf16x8_add -> same bits)
+template <bool ROWS>
 __global__ void __launch_bounds__(256) embed_decode_kernel(const int* __restrict__ tokens,
                                                           const bf16_t* __restrict__ wte,
                                                           const bf16_t* __restrict__ wpe, bf16_t* __restrict__ out,
                                                           const int* __restrict__ pos_ptr, int B, int S_max, int d,
                                                           int vocab) {
-  const int pos = pos_ptr[0];
-  if (pos < 0 || pos >= S_max) return;
   const int i = blockIdx.x * 256 + threadIdx.x, per_row = d / 8;
   if (i >= B * per_row) return;
   const int b = i / per_row, c = (i % per_row) * 8;
+  const int pos = pos_ptr[ROWS ? b : 0];
+  if (pos < 0 || pos >= S_max) return;
   const int v = tokens[(long)b * S_max + pos];
   if ((unsigned)v >= (unsigned)vocab) return;   // never read outside the table
   const u32x4 a = *reinterpret_cast<const u32x4*>(wte + (long)v * d + c);
@@ -158,6 +170,107 @@ __device__ __forceinline__ void logits8(const bf16_t* row, int i0, int V, bool v
   for (int e = 0; e < 8; ++e) x[e] = i0 + e < V ? bf2f(row[i0 + e]) : -INFINITY;
 }
 
+// Order-preserving 16-bit key of a bf16 value held in a float: a larger value has a larger
+// key.  -0 shares the key of +0 and a NaN gets key 0 (below -inf), so it is never kept.
+__device__ __forceinline__ unsigned key16(float x) {
+  unsigned h = __float_as_uint(x) >> 16;
+  if ((h & 0x7fffu) > 0x7f80u) return 0u;
+  if (h == 0x8000u) h = 0u;
+  return (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u);
+}
+
+// the sampling weight of a logit; FILT: 0 below the threshold key
+template <bool FILT>
+__device__ __forceinline__ float weight(float x, float gmx, float inv_t, unsigned thr) {
+  if (FILT && key16(x) < thr) return 0.f;
+  return __expf((x - gmx) * inv_t);
+}
+
+// inclusive prefix sum of v over the workgroup's 256 threads (every thread calls it)
+__device__ __forceinline__ int block_scan_incl(int v, int* s_tmp) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) {
+    const int t = __shfl_up(v, o, WAVE);
+    if (lane >= o) v += t;
+  }
+  __syncthreads();   // the previous call's readers are done with s_tmp
+  if (lane == WAVE - 1) s_tmp[w] = v;
+  __syncthreads();
+  int off = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    if (k < w) off += s_tmp[k];
+  return v + off;
+}
+
+// The threshold key max(key_k, key_p) of a row (every thread of the workgroup calls it and
+// gets the same value).  top-k: bf16 has 65,536 values, so two 256-bin histograms of integer
+// counts (high byte of the key, then the low byte inside the selected bin) give the key of
+// the k-th largest logit exactly.  top-p: a binary search over the key in [key_k, key(max)];
+// each probe sums the weights at or above the key in a fixed order (the thread's chunk in
+// column order, the wave, the four waves), so a row always gives the same threshold.
+__device__ __forceinline__ unsigned filter_threshold(const bf16_t* row, int V, int vec, int beg, int end, float gmx,
+                                                     float inv_t, int top_k, float top_p) {
+  __shared__ int s_hist[256], s_scan[4], s_sel[2];
+  __shared__ float s_mass[2][4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  unsigned key_k = 0;
+  if (top_k > 0 && top_k < V) {
+    int want = top_k;   // rank still to go, counted from the top of the current bin range
+    unsigned hi_bin = 0;
+    for (int level = 0; level < 2; ++level) {
+      s_hist[tid] = 0;
+      __syncthreads();
+      for (int i0 = beg; i0 < end; i0 += 8) {
+        float x[8];
+        logits8(row, i0, V, vec, x);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const unsigned key = key16(x[e]);
+          if (i0 + e < V && (level == 0 || (key >> 8) == hi_bin))
+            atomicAdd(&s_hist[level == 0 ? key >> 8 : key & 255u], 1);   // integer counts: order-free
+        }
+      }
+      __syncthreads();
+      const int bin = 255 - tid, h = s_hist[bin];   // descending: thread 0 has the top bin
+      const int inc = block_scan_incl(h, s_scan);
+      if (inc >= want && inc - h < want) {   // exactly one thread: the counts sum to >= want
+        s_sel[0] = bin;
+        s_sel[1] = want - (inc - h);
+      }
+      __syncthreads();
+      if (level == 0) hi_bin = (unsigned)s_sel[0];
+      else key_k = (hi_bin << 8) | (unsigned)s_sel[0];
+      want = s_sel[1];
+    }
+  }
+  if (!(top_p < 1.f)) return key_k;
+  int probe = 0;
+  auto mass = [&](unsigned thr) {
+    float m = 0.f;
+    for (int i0 = beg; i0 < end; i0 += 8) {
+      float x[8];
+      logits8(row, i0, V, vec, x);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) m += weight<true>(x[e], gmx, inv_t, thr);
+    }
+    m = wave_sum_dpp(m);
+    float* s = s_mass[probe++ & 1];   // two buffers: one barrier per probe
+    if (lane == 0) s[w] = m;
+    __syncthreads();
+    return (s[0] + s[1]) + (s[2] + s[3]);
+  };
+  const float target = top_p * mass(key_k);   // <= the top-k mass, so key_k always qualifies
+  unsigned lo = key_k, hi = max(key16(gmx), key_k);
+  while (lo < hi) {   // uniform: every thread sees the same masses
+    const unsigned mid = (lo + hi + 1) >> 1;
+    if (mass(mid) >= target) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
 // One workgroup per row; thread t owns the contiguous columns [t * per, (t + 1) * per).
 // temperature == 0: argmax, lowest index on ties.  Otherwise inverse-CDF sampling: weights
 // w_i = exp((x_i - max) / T) in fp32, a fixed-order prefix sum over the threads' chunk sums,
@@ -166,15 +279,39 @@ __device__ __forceinline__ void logits8(const bf16_t* row, int i0, int V, bool v
 // column whose running sum does.  The token goes to tokens[b, pos + 1]; the workgroup that
 // takes the last arrival ticket (optim.hip's scheme: every workgroup has read pos by then)
 // stores pos + 1 and re-arms the ticket.  pos + 1 >= S_max: nothing is written at all.
+//
+// ROWS: the position is pos[b] and the row is live while pos[b] + 1 < min(end[b], S_max).  Only
+// workgroup b touches pos[b] / end[b], so there is no ticket: the thread that stores the token
+// also stores pos[b] + 1 and, for a token equal to eos_id >= 0, end[b] = pos[b] + 2.
+//
+// FILT (temperature > 0 and top-k or top-p on): the weights of columns below the threshold
+// key max(key_k, key_p) are 0 and everything else runs as above.  key_k is the key of the
+// k-th largest logit (ties kept), key_p the largest key whose mass over {key >= key_p} is
+// >= top_p * (mass of the top-k set) (ties kept).
+template <bool ROWS, bool FILT>
 __global__ void __launch_bounds__(256) sample_kernel(const bf16_t* __restrict__ logits, long ld, int V,
                                                     float temperature, unsigned long long seed, unsigned stream_id,
                                                     int* __restrict__ tokens, int S_max, int* pos_ptr,
-                                                    unsigned* ticket, int vec) {
+                                                    unsigned* ticket, int vec, int* end_ptr, int eos_id, int top_k,
+                                                    float top_p) {
   __shared__ float s_mx[4], s_w[4];
   __shared__ int s_am[4], s_own[4];
-  const int pos = pos_ptr[0];
-  if (pos < 0 || pos + 1 >= S_max) return;   // uniform over the grid: the ticket stays armed at 0
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, b = blockIdx.x;
+  const int pos = pos_ptr[ROWS ? b : 0];
+  if (ROWS) {
+    if (pos < 0 || pos + 1 >= min(end_ptr[b], S_max)) return;   // finished or full: uniform over the workgroup
+  } else {
+    if (pos < 0 || pos + 1 >= S_max) return;   // uniform over the grid: the ticket stays armed at 0
+  }
+  // the one thread that stores the row's token; ROWS: it also advances / finishes the row
+  // (every thread has read pos[b] and end[b] before the first barrier, all stores come after it)
+  auto emit = [&](int tok) {
+    tokens[(long)b * S_max + pos + 1] = tok;
+    if (ROWS) {
+      pos_ptr[b] = pos + 1;
+      if (eos_id >= 0 && tok == eos_id) end_ptr[b] = pos + 2;
+    }
+  };
   const bf16_t* row = logits + (long)b * ld;
   const int per = (((V + 255) / 256) + 7) & ~7;
   const int beg = tid * per, end = min(beg + per, V);
@@ -197,17 +334,18 @@ __global__ void __launch_bounds__(256) sample_kernel(const bf16_t* __restrict__ 
   for (int k = 0; k < 4; ++k)
     if (s_mx[k] == gmx) gam = min(gam, s_am[k]);
   if (gam >= V) gam = 0;   // a row with no finite maximum
-  int* dst = tokens + (long)b * S_max + pos + 1;
   if (temperature <= 0.f) {
-    if (tid == 0) *dst = gam;
+    if (tid == 0) emit(gam);
   } else {
     const float inv_t = 1.f / temperature;
+    unsigned thr = 0;   // FILT: columns whose key is below it weigh 0
+    if (FILT) thr = filter_threshold(row, V, vec, beg, end, gmx, inv_t, top_k, top_p);
     float tsum = 0.f;
     for (int i0 = beg; i0 < end; i0 += 8) {
       float x[8];
       logits8(row, i0, V, vec, x);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) tsum += __expf((x[e] - gmx) * inv_t);
+      for (int e = 0; e < 8; ++e) tsum += weight<FILT>(x[e], gmx, inv_t, thr);
     }
     float inc = tsum;   // inclusive scan over the wave's threads
 #pragma unroll
@@ -231,7 +369,7 @@ __global__ void __launch_bounds__(256) sample_kernel(const bf16_t* __restrict__ 
     __syncthreads();
     const int owner = min(min(s_own[0], s_own[1]), min(s_own[2], s_own[3]));
     if (owner == INT_MAX) {   // u * total rounded up to total
-      if (tid == 0) *dst = gam;
+      if (tid == 0) emit(gam);
     } else if (tid == owner) {
       float run = woff + (lane > 0 ? prev : 0.f);
       int pick = -1, last = -1;
@@ -240,7 +378,7 @@ __global__ void __launch_bounds__(256) sample_kernel(const bf16_t* __restrict__ 
         logits8(row, i0, V, vec, x);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float wt = __expf((x[e] - gmx) * inv_t);
+          const float wt = weight<FILT>(x[e], gmx, inv_t, thr);
           run += wt;
           if (wt > 0.f && pick < 0) {
             last = i0 + e;
@@ -248,9 +386,10 @@ __global__ void __launch_bounds__(256) sample_kernel(const bf16_t* __restrict__ 
           }
         }
       }
-      *dst = pick >= 0 ? pick : (last >= 0 ? last : gam);
+      emit(pick >= 0 ? pick : (last >= 0 ? last : gam));
     }
   }
+  if (ROWS) return;
   __syncthreads();
   if (tid == 0) {
     const unsigned t = atomicAdd(ticket, 1u);
@@ -264,26 +403,39 @@ __global__ void __launch_bounds__(256) sample_kernel(const bf16_t* __restrict__ 
 }  // namespace jdt
 using namespace jdt;
 
+
 static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
-// qkv [B, 3*H*Dh] bf16 (q | k | v), caches [B, H, S_max, Dh] bf16, o [B, H*Dh] bf16, pos int32[1]
-JDT_API int jdt_attn_decode(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H,
-                            int Dh, int S_max, float scale, void* stream) {
+template <bool ROWS>
+static int attn_decode_launch(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H,
+                              int Dh, int S_max, float scale, void* stream) {
   if (Dh != AD_DH) return -3;
   if (S_max < 1 || S_max > AD_SMAX) return -4;
   if (B < 0 || H < 1) return -5;
   if (!qkv || !k_cache || !v_cache || !o || !pos) return -2;
   if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
   if (B == 0) return 0;
-  hipLaunchKernelGGL(attn_decode_kernel, dim3(B * H), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(attn_decode_kernel<ROWS>, dim3(B * H), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache),
                      static_cast<bf16_t*>(o), pos, H, S_max, scale);
   return HIP_LAUNCH_CHECK();
 }
 
-// out [B, d] bf16 = wte[tokens[b, pos]] + wpe[pos]; tokens int32 [B, S_max]; wpe has >= S_max rows
-JDT_API int jdt_embed_decode(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos, int B,
-                             int S_max, int d, int vocab, void* stream) {
+// qkv [B, 3*H*Dh] bf16 (q | k | v), caches [B, H, S_max, Dh] bf16, o [B, H*Dh] bf16, pos int32[1]
+JDT_API int jdt_attn_decode(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H,
+                            int Dh, int S_max, float scale, void* stream) {
+  return attn_decode_launch<false>(qkv, k_cache, v_cache, o, pos, B, H, Dh, S_max, scale, stream);
+}
+
+// as jdt_attn_decode with one position per sequence: pos int32[B]
+JDT_API int jdt_attn_decode_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H,
+                                 int Dh, int S_max, float scale, void* stream) {
+  return attn_decode_launch<true>(qkv, k_cache, v_cache, o, pos, B, H, Dh, S_max, scale, stream);
+}
+
+template <bool ROWS>
+static int embed_decode_launch(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos, int B,
+                               int S_max, int d, int vocab, void* stream) {
   if (d < 8 || d % 8) return -3;
   if (S_max < 1 || vocab < 1 || B < 0) return -5;
   if (!tokens || !wte || !wpe || !out || !pos) return -2;
@@ -291,9 +443,43 @@ JDT_API int jdt_embed_decode(const int* tokens, const void* wte, const void* wpe
   if (B == 0) return 0;
   const long n = (long)B * (d / 8);
   if (n > INT_MAX) return -5;
-  hipLaunchKernelGGL(embed_decode_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(embed_decode_kernel<ROWS>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      static_cast<hipStream_t>(stream), tokens, static_cast<const bf16_t*>(wte),
                      static_cast<const bf16_t*>(wpe), static_cast<bf16_t*>(out), pos, B, S_max, d, vocab);
+  return HIP_LAUNCH_CHECK();
+}
+
+// out [B, d] bf16 = wte[tokens[b, pos]] + wpe[pos]; tokens int32 [B, S_max]; wpe has >= S_max rows
+JDT_API int jdt_embed_decode(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos, int B,
+                             int S_max, int d, int vocab, void* stream) {
+  return embed_decode_launch<false>(tokens, wte, wpe, out, pos, B, S_max, d, vocab, stream);
+}
+
+// as jdt_embed_decode with one position per sequence: pos int32[B]
+JDT_API int jdt_embed_decode_rows(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos,
+                                  int B, int S_max, int d, int vocab, void* stream) {
+  return embed_decode_launch<true>(tokens, wte, wpe, out, pos, B, S_max, d, vocab, stream);
+}
+
+// The checks and the launch of the three sampler entry points.  ROWS: ``end`` in the place of
+// ``ticket``.  top_k = 0 (or >= V) and top_p = 1 are "off"; with both off, or at temperature 0
+// (greedy), the unfiltered kernel runs.
+template <bool ROWS>
+static int sample_launch(const void* logits, long ld, int B, int V, float temperature, unsigned long long seed,
+                         unsigned stream_id, int* tokens, int S_max, int* pos, unsigned* ticket, int* end, int eos_id,
+                         int top_k, float top_p, void* stream) {
+  if (V < 1 || ld < V || S_max < 1 || B < 0) return -5;
+  if (!(temperature >= 0.f)) return -7;
+  if (top_k < 0) return -8;
+  if (!(top_p > 0.f && top_p <= 1.f)) return -9;
+  if (!logits || !tokens || !pos || (ROWS ? !end : !ticket)) return -2;
+  if (B == 0) return 0;
+  const int vec = (V % 8 == 0) && (ld % 8 == 0) && !misaligned16(logits);
+  const bool filt = temperature > 0.f && ((top_k > 0 && top_k < V) || top_p < 1.f);
+  auto kernel = filt ? sample_kernel<ROWS, true> : sample_kernel<ROWS, false>;
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const bf16_t*>(logits), ld, V, temperature, seed, stream_id, tokens, S_max, pos,
+                     ticket, vec, end, eos_id, top_k, top_p);
   return HIP_LAUNCH_CHECK();
 }
 
@@ -301,13 +487,23 @@ JDT_API int jdt_embed_decode(const int* tokens, const void* wte, const void* wpe
 // uint32 the kernel leaves zero again
 JDT_API int jdt_sample(const void* logits, long ld, int B, int V, float temperature, unsigned long long seed,
                        unsigned stream_id, int* tokens, int S_max, int* pos, unsigned* ticket, void* stream) {
-  if (V < 1 || ld < V || S_max < 1 || B < 0) return -5;
-  if (!(temperature >= 0.f)) return -7;
-  if (!logits || !tokens || !pos || !ticket) return -2;
-  if (B == 0) return 0;
-  const int vec = (V % 8 == 0) && (ld % 8 == 0) && !misaligned16(logits);
-  hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const bf16_t*>(logits), ld, V, temperature, seed, stream_id, tokens, S_max, pos,
-                     ticket, vec);
-  return HIP_LAUNCH_CHECK();
+  return sample_launch<false>(logits, ld, B, V, temperature, seed, stream_id, tokens, S_max, pos, ticket, nullptr, -1,
+                              0, 1.f, stream);
+}
+
+// jdt_sample restricted to the top-k / top-p set: top_k >= 0 (0: off), top_p in (0, 1] (1: off)
+JDT_API int jdt_sample_filtered(const void* logits, long ld, int B, int V, float temperature, unsigned long long seed,
+                                unsigned stream_id, int* tokens, int S_max, int* pos, unsigned* ticket, int top_k,
+                                float top_p, void* stream) {
+  return sample_launch<false>(logits, ld, B, V, temperature, seed, stream_id, tokens, S_max, pos, ticket, nullptr, -1,
+                              top_k, top_p, stream);
+}
+
+// one position per sequence: pos int32[B], end int32[B] (one past the last token index a row
+// may hold); eos_id >= 0: a row that draws it is finished (end[b] = its length); no ticket
+JDT_API int jdt_sample_rows(const void* logits, long ld, int B, int V, float temperature, unsigned long long seed,
+                            unsigned stream_id, int* tokens, int S_max, int* pos, int* end, int eos_id, int top_k,
+                            float top_p, void* stream) {
+  return sample_launch<true>(logits, ld, B, V, temperature, seed, stream_id, tokens, S_max, pos, nullptr, end, eos_id,
+                             top_k, top_p, stream);
 }

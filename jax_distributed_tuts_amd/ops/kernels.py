@@ -1007,14 +1007,26 @@ def colsum_(x, out):
 # The launches of a decode step share ``pos`` (device int32[1]): the number of tokens already
 # in the cache == the index of the token being processed.  The kernels read it from memory
 # (csrc/attn_decode.hip), so a captured step replays without host bookkeeping; a position
-# outside the cache makes each of them a no-op.
+# outside the cache makes each of them a no-op.  Per-row mode: ``pos`` is int32[B], one word per
+# sequence, and the sampler also takes ``end`` int32[B] (one past the last token index a row may
+# hold); a row out of range is a no-op on its own.
 AD_HEAD_DIM, AD_MAX_ROWS = 64, 128   # envelope of jdt_attn_decode (csrc/attn_decode.hip AD_DH, AD_SMAX)
 _SAMPLE_TICKET: dict = {}
+
+
+def _per_row(pos: torch.Tensor, B: int) -> bool:
+    """``pos`` is the shared word (numel 1) or one word per sequence (numel B)."""
+    assert pos.dtype == torch.int32 and pos.numel() in (1, B), "pos must be int32[1] or int32[B]"
+    return pos.numel() != 1
 
 
 def _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out):
     """Composed torch path (any head dim / cache length, any device): reads ``pos`` on the host."""
     B, d3 = qkv.shape
+    if pos.numel() != 1:   # per row: every sequence as a batch of one at its own position
+        for b in range(B):
+            _attention_decode_torch(qkv[b:b + 1], k_cache[b:b + 1], v_cache[b:b + 1], pos[b:b + 1], H, out[b:b + 1])
+        return out
     Dh = d3 // 3 // H
     S_max = k_cache.shape[2]
     p = int(pos.item())
@@ -1034,16 +1046,17 @@ def attention_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One query token per sequence against a KV cache.  ``qkv`` [B, 3*H*Dh] bf16 (the decode
     step's QKV projection, q | k | v as in training), ``k_cache`` / ``v_cache`` [B, H, S_max, Dh]
-    bf16 (one layer), ``pos`` int32[1] -> o [B, H*Dh] bf16.  Appends the token's k / v rows at
-    row ``pos``, then attends over rows 0..pos (softmax statistics fp32, p rounded to bf16
-    before P.V, fp32 accumulate).  ``pos >= S_max``: nothing is written, ``out`` keeps its
+    bf16 (one layer), ``pos`` int32[1] (shared) or int32[B] (per row) -> o [B, H*Dh] bf16.
+    Appends the token's k / v rows at row ``pos``, then attends over rows 0..pos (softmax
+    statistics fp32, p rounded to bf16 before P.V, fp32 accumulate).  A position outside
+    ``[0, S_max)``: nothing is written for that row (shared: for any row), ``out`` keeps its
     contents.  GPU, Dh = 64 and S_max <= 128: csrc/attn_decode.hip; other GPU shapes run the
     composed torch path (which syncs on ``pos``)."""
     B, d3 = qkv.shape
     d = d3 // 3
     Dh = d // H
     assert k_cache.shape == v_cache.shape and k_cache.shape[:2] == (B, H) and k_cache.shape[3] == Dh
-    assert pos.dtype == torch.int32 and pos.numel() == 1
+    rows = _per_row(pos, B)
     S_max = k_cache.shape[2]
     if out is None:
         out = torch.zeros(B, d, dtype=torch.bfloat16, device=qkv.device)
@@ -1051,68 +1064,141 @@ def attention_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
         return _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out)
     for t in (qkv, k_cache, v_cache, out):
         assert t.is_contiguous() and t.dtype == torch.bfloat16
-    rc = _lib.lib().jdt_attn_decode(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos), B, H, Dh, S_max,
-                                    float(1.0 / (Dh ** 0.5)), _lib.stream_ptr())
-    _lib.check(rc, "jdt_attn_decode")
+    name = "jdt_attn_decode_rows" if rows else "jdt_attn_decode"
+    rc = getattr(_lib.lib(), name)(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos), B, H, Dh, S_max,
+                                   float(1.0 / (Dh ** 0.5)), _lib.stream_ptr())
+    _lib.check(rc, name)
     return out
 
 
 def embed_decode(tokens: torch.Tensor, wte: torch.Tensor, wpe: torch.Tensor, pos: torch.Tensor,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x[b] = wte[tokens[b, pos]] + wpe[pos] (bf16, the bits ``embed_fwd`` gives that row);
-    ``tokens`` int32 [B, S_max], ``pos`` int32[1].  ``pos >= S_max``: ``out`` keeps its contents."""
+    ``tokens`` int32 [B, S_max], ``pos`` int32[1] or, per row, int32[B] (row b then reads
+    ``pos[b]``).  A position outside ``[0, S_max)``: ``out`` (per row: ``out[b]``) keeps its
+    contents."""
     B, S_max = tokens.shape
     d = wte.shape[1]
-    assert tokens.dtype == torch.int32 and pos.dtype == torch.int32 and wpe.shape[0] >= S_max and wpe.shape[1] == d
+    assert tokens.dtype == torch.int32 and wpe.shape[0] >= S_max and wpe.shape[1] == d
+    rows = _per_row(pos, B)
     if out is None:
         out = torch.zeros(B, d, dtype=torch.bfloat16, device=tokens.device)
     if not _is_gpu(tokens):
-        p = int(pos.item())
-        if 0 <= p < S_max:
-            out.copy_((wte.float()[tokens[:, p].long()] + wpe.float()[p]).to(torch.bfloat16))
+        if not rows:
+            p = int(pos.item())
+            if 0 <= p < S_max:
+                out.copy_((wte.float()[tokens[:, p].long()] + wpe.float()[p]).to(torch.bfloat16))
+            return out
+        pl = pos.long()
+        idx = ((pl >= 0) & (pl < S_max)).nonzero()[:, 0]
+        if idx.numel():
+            pp = pl[idx]
+            out[idx] = (wte.float()[tokens[idx, pp].long()] + wpe.float()[pp]).to(torch.bfloat16)
         return out
     for t in (tokens, wte, wpe, out):
         assert t.is_contiguous()
     assert wte.dtype == wpe.dtype == out.dtype == torch.bfloat16 and out.shape == (B, d)
-    rc = _lib.lib().jdt_embed_decode(_ptr(tokens), _ptr(wte), _ptr(wpe), _ptr(out), _ptr(pos), B, S_max, d,
-                                     int(wte.shape[0]), _lib.stream_ptr())
-    _lib.check(rc, "jdt_embed_decode")
+    name = "jdt_embed_decode_rows" if rows else "jdt_embed_decode"
+    rc = getattr(_lib.lib(), name)(_ptr(tokens), _ptr(wte), _ptr(wpe), _ptr(out), _ptr(pos), B, S_max, d,
+                                   int(wte.shape[0]), _lib.stream_ptr())
+    _lib.check(rc, name)
     return out
 
 
+def _filter_weights(x: torch.Tensor, w: torch.Tensor, top_k: int, top_p: float) -> torch.Tensor:
+    """The sampling weights ``w`` [n, V] fp32 of the logits ``x`` with everything outside the
+    top-k / top-p set zeroed.  top-k: tau_k is the k-th largest logit of the row and
+    {x >= tau_k} is kept (ties included).  top-p, over that set: tau_p is the largest logit for
+    which the fp32 mass of {x >= tau_p} reaches top_p times the set's mass (ties included).
+    The kept set is {x >= max(tau_k, tau_p)}; it always holds the row maximum."""
+    V = x.shape[1]
+    keep = torch.ones_like(x, dtype=torch.bool)
+    if 0 < top_k < V:
+        keep = x >= torch.topk(x, top_k, dim=-1).values[:, -1:]
+    if top_p < 1.0:
+        xs, order = torch.sort(x, dim=-1, descending=True, stable=True)
+        cum = torch.cumsum(torch.where(keep, w, torch.zeros_like(w)).gather(1, order), -1)
+        first = (cum >= cum[:, -1:] * float(top_p)).to(torch.uint8).argmax(-1)   # ends inside tau_p's tie group
+        keep = keep & (x >= xs.gather(1, first[:, None]))
+    return torch.where(keep, w, torch.zeros_like(w))
+
+
 def sample_tokens(logits: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor, *, temperature: float = 0.0,
-                  seed: int = 0, stream_id: int = 0) -> torch.Tensor:
+                  seed: int = 0, stream_id: int = 0, end: Optional[torch.Tensor] = None, eos_id: int = -1,
+                  top_k: int = 0, top_p: float = 1.0) -> torch.Tensor:
     """One token per row of ``logits`` [B, V] bf16 into ``tokens[:, pos + 1]`` (int32 [B, S_max]),
     then ``pos += 1``.  ``temperature == 0``: argmax, lowest index on ties; otherwise inverse-CDF
     sampling of softmax(logits / T) in fp32 with one uniform per row: word 0 of
     philox4x32(seed, counter = row, offset = (pos << 32) | stream_id) (``philox_uniform``).
-    ``pos + 1 >= S_max``: no token is written and ``pos`` stays."""
+    ``pos + 1 >= S_max``: no token is written and ``pos`` stays.
+
+    ``top_k`` (0: off) / ``top_p`` (1.0: off) restrict the draw to the set ``_filter_weights``
+    describes (applied after the temperature, ignored when greedy); with both off the drawn
+    tokens are the unfiltered sampler's.
+
+    Per-row mode (``pos`` int32[B], or ``end`` given): row b writes ``tokens[b, pos[b] + 1]`` and
+    advances ``pos[b]`` iff ``0 <= pos[b]`` and ``pos[b] + 1 < min(end[b], S_max)``; ``end`` int32[B]
+    defaults to ``S_max`` everywhere.  ``eos_id >= 0``: a row that writes that token gets
+    ``end[b] = pos[b] + 2`` -- it is finished, with the EOS as its last token."""
     B, V = logits.shape
     S_max = tokens.shape[1]
-    assert tokens.dtype == torch.int32 and tokens.shape[0] == B and pos.dtype == torch.int32 and pos.numel() == 1
+    assert tokens.dtype == torch.int32 and tokens.shape[0] == B
+    rows = _per_row(pos, B) or end is not None
     assert temperature >= 0.0 and 0 <= stream_id < 2 ** 32
+    if top_k < 0 or not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_k must be >= 0 and top_p in (0, 1], got top_k={top_k} top_p={top_p}")
+    if rows:
+        assert pos.numel() == B, "per-row sampling needs pos int32[B]"
+        if end is None:
+            end = torch.full((B,), S_max, dtype=torch.int32, device=pos.device)
+        assert end.dtype == torch.int32 and end.numel() == B
+    else:
+        assert eos_id < 0, "eos_id needs the per-row state (pos int32[B] and end)"
     seed = int(seed) & (2 ** 64 - 1)
     if not _is_gpu(logits):
-        p = int(pos.item())
-        if p < 0 or p + 1 >= S_max:
+        pv = pos.long() if rows else pos.long().expand(B)
+        lim = end.long().clamp(max=S_max) if rows else S_max
+        idx = ((pv >= 0) & (pv + 1 < lim)).nonzero()[:, 0]   # the live rows (shared: all or none)
+        if idx.numel() == 0:
             return tokens
-        x = _bf(logits.float())
+        x = _bf(logits.float())[idx]
+        pl = pv[idx]
         tok = x.argmax(-1)
         if temperature > 0.0:
             w = torch.exp((x - x.max(-1, keepdim=True).values) / float(temperature))
+            if 0 < top_k < V or top_p < 1.0:
+                w = _filter_weights(x, w, int(top_k), float(top_p))
             cum = torch.cumsum(w, -1)
-            u = torch.from_numpy(philox_uniform(seed, (p << 32) | int(stream_id), np.arange(B), 0)).float()
+            u = torch.empty(idx.numel(), dtype=torch.float32)
+            for p in pl.unique().tolist():   # one Philox offset per distinct position
+                sel = pl == p
+                u[sel] = torch.from_numpy(philox_uniform(seed, (p << 32) | int(stream_id), idx[sel].numpy(), 0)).float()
             hit = cum > (u * cum[:, -1])[:, None]
             tok = torch.where(hit.any(-1), hit.to(torch.uint8).argmax(-1), tok)   # first column past the target
-        tokens[:, p + 1] = tok.to(torch.int32)
-        pos.add_(1)
+        tokens[idx, pl + 1] = tok.to(torch.int32)
+        if rows:
+            pos[idx] += 1
+            if eos_id >= 0:
+                fin = idx[tok == eos_id]
+                end[fin] = (pv[fin] + 2).to(torch.int32)
+        else:
+            pos.add_(1)
         return tokens
     assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and tokens.is_contiguous()
+    L, head = _lib.lib(), (_ptr(logits), logits.stride(0), B, V, float(temperature), seed, int(stream_id),
+                           _ptr(tokens), S_max, _ptr(pos))
+    if rows:
+        rc = L.jdt_sample_rows(*head, _ptr(end), int(eos_id), int(top_k), float(top_p), _lib.stream_ptr())
+        _lib.check(rc, "jdt_sample_rows")
+        return tokens
     key = str(logits.device)
     ticket = _SAMPLE_TICKET.get(key)
     if ticket is None:   # the kernel leaves it zero again: one word serves every call on the device
         ticket = _SAMPLE_TICKET[key] = torch.zeros(1, dtype=torch.int32, device=logits.device)
-    rc = _lib.lib().jdt_sample(_ptr(logits), logits.stride(0), B, V, float(temperature), seed, int(stream_id),
-                               _ptr(tokens), S_max, _ptr(pos), _ptr(ticket), _lib.stream_ptr())
-    _lib.check(rc, "jdt_sample")
+    if top_k == 0 and top_p == 1.0:
+        rc = L.jdt_sample(*head, _ptr(ticket), _lib.stream_ptr())
+        _lib.check(rc, "jdt_sample")
+    else:
+        rc = L.jdt_sample_filtered(*head, _ptr(ticket), int(top_k), float(top_p), _lib.stream_ptr())
+        _lib.check(rc, "jdt_sample_filtered")
     return tokens

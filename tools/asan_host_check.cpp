@@ -38,6 +38,16 @@ int jdt_embed_decode(const int* tokens, const void* wte, const void* wpe, void* 
                      int d, int vocab, void* stream);
 int jdt_sample(const void* logits, long ld, int B, int V, float temperature, unsigned long long seed,
                unsigned stream_id, int* tokens, int S_max, int* pos, unsigned* ticket, void* stream);
+int jdt_attn_decode_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H, int Dh,
+                         int S_max, float scale, void* stream);
+int jdt_embed_decode_rows(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos, int B,
+                          int S_max, int d, int vocab, void* stream);
+int jdt_sample_filtered(const void* logits, long ld, int B, int V, float temperature, unsigned long long seed,
+                        unsigned stream_id, int* tokens, int S_max, int* pos, unsigned* ticket, int top_k, float top_p,
+                        void* stream);
+int jdt_sample_rows(const void* logits, long ld, int B, int V, float temperature, unsigned long long seed,
+                    unsigned stream_id, int* tokens, int S_max, int* pos, int* end, int eos_id, int top_k, float top_p,
+                    void* stream);
 }
 
 static int failures = 0;
@@ -96,6 +106,48 @@ int main() {
   EXPECT(jdt_sample(buf, 8, 1, 8, -1.f, 0, 0, ip, 128, ip, up, nullptr) == -7, "sample rejects temperature < 0");
   EXPECT(jdt_sample(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, ip, nullptr, nullptr) == -2, "sample rejects a null ticket");
   EXPECT(jdt_sample(buf, 8, 0, 8, 1.f, 0, 0, ip, 128, ip, up, nullptr) == 0, "sample B = 0 is a no-op");
+  // per-row and filtered variants: the same envelope, plus top_k / top_p
+  EXPECT(jdt_attn_decode_rows(buf, buf, buf, buf, ip, 1, 2, 32, 128, .125f, nullptr) == -3,
+         "attn_decode_rows rejects head dim 32");
+  EXPECT(jdt_attn_decode_rows(buf, buf, buf, buf, ip, 1, 2, 64, 129, .125f, nullptr) == -4,
+         "attn_decode_rows rejects S_max > 128");
+  EXPECT(jdt_attn_decode_rows(buf, buf, buf, buf, ip, 1, 2, 64, 0, .125f, nullptr) == -4,
+         "attn_decode_rows rejects S_max 0");
+  EXPECT(jdt_attn_decode_rows(buf, buf, buf, buf, nullptr, 1, 2, 64, 128, .125f, nullptr) == -2,
+         "attn_decode_rows rejects a null pos");
+  EXPECT(jdt_attn_decode_rows(buf, buf, buf, buf, ip, 0, 2, 64, 128, .125f, nullptr) == 0,
+         "attn_decode_rows B = 0 is a no-op");
+  EXPECT(jdt_embed_decode_rows(ip, buf, buf, buf, nullptr, 1, 128, 64, 8, nullptr) == -2,
+         "embed_decode_rows rejects a null pos");
+  EXPECT(jdt_embed_decode_rows(ip, buf, buf, buf, ip, 1, 0, 64, 8, nullptr) == -5, "embed_decode_rows rejects S_max 0");
+  EXPECT(jdt_embed_decode_rows(ip, buf, buf, buf, ip, 0, 128, 64, 8, nullptr) == 0,
+         "embed_decode_rows B = 0 is a no-op");
+  EXPECT(jdt_sample_filtered(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, ip, up, -1, 1.f, nullptr) == -8,
+         "sample_filtered rejects top_k < 0");
+  EXPECT(jdt_sample_filtered(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, ip, up, 0, 0.f, nullptr) == -9,
+         "sample_filtered rejects top_p = 0");
+  EXPECT(jdt_sample_filtered(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, ip, up, 0, 1.5f, nullptr) == -9,
+         "sample_filtered rejects top_p > 1");
+  EXPECT(jdt_sample_filtered(buf, 8, 1, 8, 1.f, 0, 0, ip, 0, ip, up, 3, .9f, nullptr) == -5,
+         "sample_filtered rejects S_max 0");
+  EXPECT(jdt_sample_filtered(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, ip, nullptr, 3, .9f, nullptr) == -2,
+         "sample_filtered rejects a null ticket");
+  EXPECT(jdt_sample_filtered(buf, 8, 0, 8, 1.f, 0, 0, ip, 128, ip, up, 3, .9f, nullptr) == 0,
+         "sample_filtered B = 0 is a no-op");
+  EXPECT(jdt_sample_rows(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, ip, ip, -1, -1, 1.f, nullptr) == -8,
+         "sample_rows rejects top_k < 0");
+  EXPECT(jdt_sample_rows(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, ip, ip, -1, 0, 0.f, nullptr) == -9,
+         "sample_rows rejects top_p = 0");
+  EXPECT(jdt_sample_rows(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, ip, ip, -1, 0, 1.5f, nullptr) == -9,
+         "sample_rows rejects top_p > 1");
+  EXPECT(jdt_sample_rows(buf, 8, 1, 8, 1.f, 0, 0, ip, 0, ip, ip, -1, 0, 1.f, nullptr) == -5,
+         "sample_rows rejects S_max 0");
+  EXPECT(jdt_sample_rows(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, ip, nullptr, -1, 0, 1.f, nullptr) == -2,
+         "sample_rows rejects a null end");
+  EXPECT(jdt_sample_rows(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, nullptr, ip, -1, 0, 1.f, nullptr) == -2,
+         "sample_rows rejects a null pos");
+  EXPECT(jdt_sample_rows(buf, 8, 0, 8, 1.f, 0, 0, ip, 128, ip, ip, 3, 50, .9f, nullptr) == 0,
+         "sample_rows B = 0 is a no-op");
   std::printf("asan host check: %d failure(s)\n", failures);
   return failures ? 1 : 0;
 }

@@ -2,10 +2,13 @@
 default TransformerConfig at B = 1 and B = 16: us per decode step and tokens/s, launched
 eagerly against one captured step replayed per token, plus the kernel-launcher calls per step.
 
-    python tools/bench_generate.py [--steps 100] [--temperature 0.0]
+    python tools/bench_generate.py [--steps 100] [--temperature 0.0] [--ragged]
 
 Each figure: ``--steps`` decode steps after a 16-token prefill, timed with events around the
-whole loop (prefill excluded), median of 5 runs.
+whole loop (prefill excluded), median of 5 runs.  ``--ragged`` adds, at B = 16 and a sampling
+temperature (``--temperature``, or 0.8 when that is 0): the uniform batch with the top-k /
+top-p sampler (k = 50, p = 0.9), and a ragged batch (prompt lengths 1..16, per-row positions)
+with the plain and with the filtered sampler.
 """
 import argparse
 import os
@@ -69,6 +72,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--temperature", type=float, default=0.0)
+    ap.add_argument("--ragged", action="store_true", help="extra lines: top-k / top-p and a ragged B = 16 batch")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     cfg = TransformerConfig()
@@ -91,6 +95,26 @@ def main():
             line += f" | captured {t_g:7.1f} us/step ({B / t_g * 1e6:9.0f} tokens/s)"
         print(line + f" | {sum(calls.values())} launcher calls/step: "
               + ", ".join(f"{k[4:]} x{v}" for k, v in sorted(calls.items())), flush=True)
+    if not a.ragged:
+        return
+    B, T = 16, a.temperature or 0.8
+    prompt = torch.randint(0, cfg.vocab_size, (B, PROMPT), generator=torch.Generator().manual_seed(1))
+    prompt = prompt.to(torch.int32).to(dev)
+    for lens in (None, torch.arange(1, B + 1)):
+        for top_k, top_p in ((0, 1.0), (50, 0.9)):
+            if lens is None and top_k == 0:
+                continue   # the uniform batch with the plain sampler: the lines above
+            gen = Generator(model, P, B, dev)
+            gen.generate(prompt, 2, temperature=T, capture=True, prompt_lens=lens, top_k=top_k, top_p=top_p)
+            graph = gen._graphs[gen._graph_key()][0]
+            reset = lambda: gen.prefill(prompt, lens)  # noqa: E731  (end = seq_len: no row finishes in the loop)
+            t_e = timed(gen.step, reset, a.steps)
+            line = (f"generate B={B:2d} T={T} {'ragged ' if lens is not None else 'uniform'} top_k={top_k:2d} "
+                    f"top_p={top_p}: eager {t_e:7.1f} us/step")
+            if graph is not None:
+                t_g = timed(graph.replay, reset, a.steps)
+                line += f" | captured {t_g:7.1f} us/step ({B / t_g * 1e6:9.0f} tokens/s)"
+            print(line, flush=True)
 
 
 if __name__ == "__main__":
