@@ -6,14 +6,17 @@ one captured decode step replayed per token).
     python generate.py --train-steps 200 --temperature 0.8 --seed 3   # train on lm_batch first
     python generate.py --restore ckpt_dir                             # weights of a checkpoint
     python generate.py --batch 3 --prompt-lens 5,16,9 --temperature 0.8 --top-k 50 --top-p 0.9 --eos-id 7
+    python generate.py --seq-len 1024 --prompt-len 900 --max-new-tokens 100   # a 1024-row KV cache
 
 Runs the HIP kernels on a GPU and the torch reference paths on CPU tensors when none is
 present.  The prompt is the first ``--prompt-len`` tokens of ``lm_batch``'s sequences;
 ``--prompt-lens`` gives every sequence its own length (ragged prompts), ``--top-k`` /
 ``--top-p`` restrict the sampler and ``--eos-id`` ends a sequence at that token.  Each row is
-printed up to its own final length.
-Not covered: beam search, repetition penalties, sequences past ``seq_len``, multi-GPU or
-pipeline-split generation.
+printed up to its own final length.  ``--seq-len`` builds the LM with that many learned
+positions (default 128); up to 32768 the decode attention stays on the HIP kernels (split-KV
+past 128 cache rows).
+Not covered: beam search, repetition penalties, sequences past ``seq_len``, caches longer than
+32768 rows or head dims other than 64 on the HIP path, multi-GPU or pipeline-split generation.
 """
 from __future__ import annotations
 
@@ -23,15 +26,36 @@ import time
 import torch
 
 from jax_distributed_tuts_amd.generation import Generator
+from jax_distributed_tuts_amd.models.transformer import TransformerConfig
 from jax_distributed_tuts_amd.parallel.pipeline_lm import build_lm_pipeline, lm_batch
 from jax_distributed_tuts_amd.utils.train_state import Batch
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--train-steps", type=int, default=0, help="AdamW steps on lm_batch before generating")
+    ap.add_argument("--restore", default=None, metavar="DIR", help="load a utils.checkpoint directory first")
+    ap.add_argument("--prompt-len", type=int, default=16)
+    ap.add_argument("--max-new-tokens", type=int, default=32)
+    ap.add_argument("--temperature", type=float, default=0.0, help="0: greedy")
+    ap.add_argument("--seed", type=int, default=0, help="sampling seed (Philox stream)")
+    ap.add_argument("--top-k", type=int, default=0, help="sample from the k largest logits only (0: off)")
+    ap.add_argument("--top-p", type=float, default=1.0, help="nucleus sampling mass in (0, 1] (1: off)")
+    ap.add_argument("--eos-id", type=int, default=None, help="a sequence that emits this token stops there")
+    ap.add_argument("--prompt-lens", default=None, metavar="L0,L1,...",
+                    help="one prompt length per sequence (ragged prompts); overrides --prompt-len")
+    ap.add_argument("--model-seed", type=int, default=0, help="parameter initialisation seed")
+    ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--seq-len", type=int, default=128, help="learned positions == rows of the KV cache")
+    ap.add_argument("--eager", action="store_true", help="launch every decode step eagerly (no graph replay)")
+    return ap.parse_args(argv)
 
 
 def main(args):
     dev = torch.device("cuda", 0) if torch.cuda.is_available() else torch.device("cpu")
     if dev.type == "cuda":
         torch.cuda.set_device(dev)
-    tr, cfg = build_lm_pipeline(None, dev, seed=args.model_seed)
+    tr, cfg = build_lm_pipeline(None, dev, cfg=TransformerConfig(seq_len=args.seq_len), seed=args.model_seed)
     if args.restore:
         from jax_distributed_tuts_amd.utils.checkpoint import restore
 
@@ -71,19 +95,4 @@ def main(args):
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--train-steps", type=int, default=0, help="AdamW steps on lm_batch before generating")
-    ap.add_argument("--restore", default=None, metavar="DIR", help="load a utils.checkpoint directory first")
-    ap.add_argument("--prompt-len", type=int, default=16)
-    ap.add_argument("--max-new-tokens", type=int, default=32)
-    ap.add_argument("--temperature", type=float, default=0.0, help="0: greedy")
-    ap.add_argument("--seed", type=int, default=0, help="sampling seed (Philox stream)")
-    ap.add_argument("--top-k", type=int, default=0, help="sample from the k largest logits only (0: off)")
-    ap.add_argument("--top-p", type=float, default=1.0, help="nucleus sampling mass in (0, 1] (1: off)")
-    ap.add_argument("--eos-id", type=int, default=None, help="a sequence that emits this token stops there")
-    ap.add_argument("--prompt-lens", default=None, metavar="L0,L1,...",
-                    help="one prompt length per sequence (ragged prompts); overrides --prompt-len")
-    ap.add_argument("--model-seed", type=int, default=0, help="parameter initialisation seed")
-    ap.add_argument("--batch", type=int, default=2)
-    ap.add_argument("--eager", action="store_true", help="launch every decode step eagerly (no graph replay)")
-    main(ap.parse_args())
+    main(parse_args())

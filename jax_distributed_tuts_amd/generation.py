@@ -12,7 +12,13 @@ Prefill convention: ``prefill(prompt)`` runs the training forward once over the 
 padded to ``seq_len`` (causal attention makes rows < P independent of the padding),
 copies rows < P of every layer's k / v into the cache and sets ``pos = P - 1``: the first
 decode step re-processes the last prompt token (rewriting cache row P - 1 with its own
-k / v) and samples token P from it.
+k / v) and samples token P from it.  With ``seq_len > 128`` the forward runs over the prompt
+padded to the next multiple of 128 only (``Generator.prefill_rows``), not over the whole cache.
+
+Long caches: the decode attention is one launch up to 128 cache rows and, for ``128 < seq_len
+<= 32768``, a split-KV pair of launches (one workgroup per 128-key chunk, then a combine;
+``KVCache.split_ws`` holds the partials).  Both read ``pos`` on the device and their grids
+depend on the cache's shape only, so the captured step replays at every depth.
 
 Ragged batches: ``prefill(prompt, prompt_lens)`` / ``generate(..., prompt_lens=, eos_id=)``
 switch the cache to its per-row state, ``pos_rows`` int32[B] and ``end`` int32[B] (one past
@@ -24,10 +30,12 @@ The sampler can also be restricted to the top-k / top-p set (``ops.kernels.sampl
 
 Out of scope: beam search, repetition penalties, sequences longer than ``seq_len`` (the
 learned positions end there), multi-GPU or pipeline-split generation, paged or compacted
-caches, removing finished rows from the batch, and head dims other than 64 on the HIP path.
+caches, chunked prefill into the cache, removing finished rows from the batch, and head dims
+other than 64 or caches past 32768 rows on the HIP path.
 """
 from __future__ import annotations
 
+import dataclasses
 from typing import Optional
 
 import torch
@@ -43,7 +51,9 @@ class KVCache:
     device position word ``pos`` int32[1] and ``o``, the decode step's attention output
     ``[B, d_model]`` bf16 (one buffer, reused layer after layer).  The per-row state is
     ``pos_rows`` int32[B] and ``end`` int32[B] (one past the last token index a row may hold);
-    ``per_row`` says which position tensor is live (``live_pos``): ``pos`` by default."""
+    ``per_row`` says which position tensor is live (``live_pos``): ``pos`` by default.
+    ``split_ws``: the split-KV decode attention's partials, fp32 ``[B * H, ceil(seq_len / 128),
+    66]`` (one buffer, reused layer after layer), or ``None`` when ``seq_len <= 128``."""
 
     def __init__(self, cfg: TransformerConfig, batch: int, device):
         H, Dh = cfg.n_heads, cfg.d_model // cfg.n_heads
@@ -57,6 +67,10 @@ class KVCache:
         self.per_row = False
         # attention output of the layer in flight (a step past the end leaves it as it is)
         self.o = torch.zeros(batch, cfg.d_model, dtype=torch.bfloat16, device=device)
+        self.split_ws: Optional[torch.Tensor] = None
+        if cfg.seq_len > K.AD_CHUNK_ROWS:
+            chunks = (cfg.seq_len + K.AD_CHUNK_ROWS - 1) // K.AD_CHUNK_ROWS
+            self.split_ws = torch.zeros(batch * H, chunks, K.AD_SLOT_FLOATS, dtype=torch.float32, device=device)
 
     @property
     def live_pos(self) -> torch.Tensor:
@@ -78,6 +92,8 @@ class Generator:
         self.top_k, self.top_p, self.eos_id = 0, 1.0, -1
         self.logits: Optional[torch.Tensor] = None   # the last step's logits [B, vocab]
         self.lengths: Optional[torch.Tensor] = None  # int32 [B]: the final lengths of the last generate
+        self.prefill_rows = 0                        # rows per sequence the last prefill's forward ran over
+        self._prefill_models: dict = {}              # rows -> the model at that seq_len (same parameters)
         # (temperature, seed) -> (graph, its logits); any other sampler setting or the
         # per-row mode: (temperature, seed, top_k, top_p, eos_id, per_row)
         self._graphs: dict = {}
@@ -89,7 +105,11 @@ class Generator:
         ``prompt_lens`` (int [B], each in 1..P): ``prompt`` is right-padded, tokens at or past
         a row's length are ignored, and the per-row state becomes live: ``pos_rows[b] =
         len_b - 1``, ``end[b] = seq_len``.  Cache rows >= len_b of row b are never read before
-        the decode step writes them."""
+        the decode step writes them.
+
+        ``seq_len > 128``: the forward runs over ``prefill_rows`` = P rounded up to a multiple of
+        128 (at most ``seq_len``) rows per sequence: a model of that ``seq_len`` on the same
+        parameters (the embedding reads only the first ``prefill_rows`` rows of ``wpe``)."""
         c = self.model.cfg
         if prompt.dim() != 2 or prompt.shape[0] != self.batch or not 1 <= prompt.shape[1] <= c.seq_len:
             raise ValueError(f"prompt must be [{self.batch}, 1..{c.seq_len}], got {tuple(prompt.shape)}")
@@ -107,9 +127,17 @@ class Generator:
         kv = self.kv
         kv.tokens.zero_()
         kv.tokens[:, :Pn] = prompt
-        _, cache = self.model.forward(self.P, kv.tokens)
+        model, Sp = self.model, c.seq_len
+        if c.seq_len > K.AD_CHUNK_ROWS:
+            Sp = min(-(-Pn // K.AD_CHUNK_ROWS) * K.AD_CHUNK_ROWS, c.seq_len)
+            if Sp != c.seq_len:
+                model = self._prefill_models.get(Sp)
+                if model is None:
+                    model = self._prefill_models[Sp] = TransformerLM(dataclasses.replace(c, seq_len=Sp))
+        self.prefill_rows = Sp
+        _, cache = model.forward(self.P, kv.tokens if Sp == c.seq_len else kv.tokens[:, :Sp].contiguous())
         for l, bc in zip(self.model.layers, cache.blocks):
-            qkv = bc.qkv.view(B, c.seq_len, 3, H, Dh)
+            qkv = bc.qkv.view(B, Sp, 3, H, Dh)
             kv.k[l][:, :, :Pn] = qkv[:, :Pn, 1].permute(0, 2, 1, 3)
             kv.v[l][:, :, :Pn] = qkv[:, :Pn, 2].permute(0, 2, 1, 3)
         kv.per_row = lens is not None

@@ -216,7 +216,8 @@ class TransformerLM:
         ``kv.pos`` (``ops.kernels.embed_decode``), ``kv`` a ``generation.KVCache``; returns
         the logits [B, vocab] bf16.  The same ``ln_gemm`` / ``gemm`` calls as ``forward`` at
         M = B, with ``attention_decode`` (appends to layer l's cache, attends over rows
-        0..pos) in the place of ``attention_fwd``.  The position is the cache's live tensor:
+        0..pos; past 128 cache rows its partials go through ``kv.split_ws``) in the place of
+        ``attention_fwd``.  The position is the cache's live tensor:
         ``kv.pos_rows`` (one word per sequence) when ``kv.per_row`` is set, else ``kv.pos``; it
         is only read."""
         if not (self.has_embed and self.has_head):
@@ -229,7 +230,7 @@ class TransformerLM:
             b = f"block_{l}"
             qkv, _, _, _ = K.ln_gemm(h, P.p(f"{b}/ln1/scale"), P.p(f"{b}/ln1/bias"), P.s(f"{b}/attn/qkv/kernel"),
                                      eps=c.ln_eps, bias=P.s(f"{b}/attn/qkv/bias"))
-            o = K.attention_decode(qkv, kv.k[l], kv.v[l], pos, c.n_heads, out=kv.o)
+            o = K.attention_decode(qkv, kv.k[l], kv.v[l], pos, c.n_heads, out=kv.o, ws=getattr(kv, "split_ws", None))
             x2 = K.gemm(o, P.s(f"{b}/attn/out/kernel"), bias=P.s(f"{b}/attn/out/bias"), resid=h)
             # z_out as in forward: the GELU then sees the pre-activation rounded to bf16
             z1 = torch.empty(x2.shape[0], c.d_ff, dtype=torch.bfloat16, device=x2.device)

@@ -124,6 +124,12 @@ _SIGS = {
                                      c_float, c_void_p]),
     "jdt_embed_decode_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                       c_void_p]),
+    # split-KV decode attention (S_max <= 32768), shared / per-row positions:
+    # (qkv, k_cache, v_cache, o, pos, ws, ws_floats, B, H, Dh, S_max, scale, stream)
+    "jdt_attn_decode_long": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int,
+                                     c_int, c_int, c_float, c_void_p]),
+    "jdt_attn_decode_long_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int,
+                                          c_int, c_int, c_int, c_float, c_void_p]),
     # (logits, ld, B, V, temperature, seed, stream_id, tokens, S_max, pos, ticket, top_k, top_p, stream)
     "jdt_sample_filtered": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_ulonglong, ctypes.c_uint, c_void_p,
                                     c_int, c_void_p, c_void_p, c_int, c_float, c_void_p]),

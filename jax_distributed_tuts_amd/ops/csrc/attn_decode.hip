@@ -17,7 +17,11 @@
 //
 // attn_decode:  single-query attention.  M = 1: latency / memory bound, no MFMA and no
 //               LDS staging -- each cached K / V row goes straight to VGPRs with one
-//               16-byte load per 8 lanes' slice and is read exactly once.
+//               16-byte load per 8 lanes' slice and is read exactly once.  Caches of up to
+//               AD_SMAX rows: one launch.  Longer caches (the ``_long`` launchers, up to
+//               AD_LONG_SMAX rows): the same body once per 128-key chunk (split-KV), each
+//               workgroup leaving an unnormalised partial in a workspace slot, then a second
+//               launch that folds the partials -- the kernel boundary is the hand-off.
 // embed_decode: x[b] = wte[tokens[b, pos]] + wpe[pos]   (the bits embed_fwd_kernel stores)
 // sample:       argmax (temperature 0) or inverse-CDF sampling of softmax(logits / T),
 //               optionally restricted to the top-k / top-p set (FILT = true)
@@ -31,6 +35,10 @@ constexpr int AD_DH = 64;      // head dim (8 lanes x 8 bf16 = one 128-byte row)
 constexpr int AD_SMAX = 128;   // cache rows per head the kernel covers
 constexpr int AD_KPP = 32;     // keys per pass: 256 threads / 8 lanes per key
 constexpr int AD_NP = AD_SMAX / AD_KPP;
+constexpr int AD_CHUNK = AD_KPP * AD_NP;   // keys per workgroup of the split-KV launch
+constexpr int AD_LONG_SMAX = 32768;        // cache rows per head the split-KV launchers cover
+constexpr int AD_SLOT = 2 + AD_DH;         // fp32 words of a partial: max, sum, unnormalised o[64]
+constexpr int AD_CB = 8;                   // partials the combine loads at a time
 
 __device__ __forceinline__ void unpack8(const u32x4& r, float (&x)[8]) {
 #pragma unroll
@@ -55,23 +63,39 @@ __device__ __forceinline__ float oct_sum_dpp(float v) {
 // over keys 0..pos, fp32 softmax statistics, p = exp(s - max) rounded to bf16 before P.V and
 // the fp32 sum scaled by 1 / l at the end (the rounding points of the training forward,
 // attn128.hip), o stored as bf16.
-template <bool ROWS>
+//
+// SPLIT: workgroup (bh, blockIdx.y = ch) does the same over the keys of chunk ch, rows
+// [128 ch, min(128 ch + 128, pos + 1)), and returns at once when the chunk starts past the
+// position.  Below, ``pos`` is the position relative to the chunk's first row: >= AD_CHUNK for a
+// chunk that is full (every row comes from the cache, nothing is appended), else the chunk holds
+// the token itself.  Instead of normalising, the workgroup stores its partial into workspace
+// slot (bh, ch): the chunk's max m, l = sum exp(s - m) and the unnormalised fp32 o[64].
+// The grid, (B * H, ceil(S_max / AD_CHUNK)), depends on the cache's shape only, never on pos.
+// ``o`` is unused with SPLIT and ``ws`` without it.
+template <bool ROWS, bool SPLIT>
 __global__ void __launch_bounds__(256) attn_decode_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
                                                          bf16_t* __restrict__ vc, bf16_t* __restrict__ o,
                                                          const int* __restrict__ pos_ptr, int H, int S_max,
-                                                         float scale) {
+                                                         float scale, float* __restrict__ ws) {
   __shared__ float red_m[4], red_l[4], red_o[4][AD_DH];
   const int bh = blockIdx.x, b = bh / H, h = bh % H;
-  const int pos = pos_ptr[ROWS ? b : 0];
-  if (pos < 0 || pos >= S_max) return;   // past the end: nothing is written (uniform over the workgroup)
+  const int tok_pos = pos_ptr[ROWS ? b : 0];
+  if (tok_pos < 0 || tok_pos >= S_max) return;   // past the end: nothing is written (uniform over the workgroup)
+  const int row0 = SPLIT ? (int)blockIdx.y * AD_CHUNK : 0;
+  if (SPLIT && row0 > tok_pos) return;   // a chunk past the position: no partial, its slot is never read
+  const int pos = tok_pos - row0;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = tid & 7, g = tid >> 3;
   const long d = (long)H * AD_DH;
   const bf16_t* row = qkv + (long)b * 3 * d + h * AD_DH + c * 8;
   const u32x4 qv = *reinterpret_cast<const u32x4*>(row);
   const u32x4 kn = *reinterpret_cast<const u32x4*>(row + d);
   const u32x4 vn = *reinterpret_cast<const u32x4*>(row + 2 * d);
-  bf16_t* Kh = kc + (long)bh * S_max * AD_DH + c * 8;
+  bf16_t* Kh = kc + (long)bh * S_max * AD_DH + c * 8;   // SPLIT: the chunk's first row
   bf16_t* Vh = vc + (long)bh * S_max * AD_DH + c * 8;
+  if (SPLIT) {
+    Kh += (long)row0 * AD_DH;
+    Vh += (long)row0 * AD_DH;
+  }
   // every load of the step is issued before the first use; rows past pos are never read
   u32x4 kr[AD_NP], vr[AD_NP];
 #pragma unroll
@@ -85,7 +109,7 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const bf16_t* __restri
       vr[i] = vn;
     }
   }
-  if (g == (pos & (AD_KPP - 1))) {
+  if ((!SPLIT || pos < AD_CHUNK) && g == (pos & (AD_KPP - 1))) {
     *reinterpret_cast<u32x4*>(Kh + (long)pos * AD_DH) = kn;
     *reinterpret_cast<u32x4*>(Vh + (long)pos * AD_DH) = vn;
   }
@@ -136,9 +160,63 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const bf16_t* __restri
   }
   __syncthreads();
   if (tid < AD_DH) {
-    const float inv = 1.f / l;
-    o[(long)b * d + h * AD_DH + tid] = f2bf(((red_o[0][tid] + red_o[1][tid]) + (red_o[2][tid] + red_o[3][tid])) * inv);
+    if (SPLIT) {
+      float* slot = ws + ((long)bh * gridDim.y + blockIdx.y) * AD_SLOT;
+      if (tid == 0) {
+        slot[0] = m;
+        slot[1] = l;
+      }
+      slot[2 + tid] = (red_o[0][tid] + red_o[1][tid]) + (red_o[2][tid] + red_o[3][tid]);
+    } else {
+      const float inv = 1.f / l;
+      o[(long)b * d + h * AD_DH + tid] =
+          f2bf(((red_o[0][tid] + red_o[1][tid]) + (red_o[2][tid] + red_o[3][tid])) * inv);
+    }
   }
+}
+
+// The second launch of the split-KV path: one wave per (batch, head), lane t owns column t.
+// Folds the partials of chunks 0..pos / 128 in increasing order: M = max m_c, L = sum l_c e^(m_c - M),
+// o = (sum o_c e^(m_c - M)) * (1 / L), stored as bf16.  Slots past pos / 128 are never read (stale
+// workspace contents are harmless) and a position outside the cache leaves o as it is.  One chunk:
+// e^0 = 1, so this is o_0 * (1 / l_0) -- the expression and the bits of attn_decode_kernel.
+template <bool ROWS>
+__global__ void __launch_bounds__(WAVE) attn_decode_combine_kernel(const float* __restrict__ ws,
+                                                                  bf16_t* __restrict__ o,
+                                                                  const int* __restrict__ pos_ptr, int H, int S_max,
+                                                                  int n_chunks) {
+  const int bh = blockIdx.x, b = bh / H, h = bh % H, t = threadIdx.x;
+  const int pos = pos_ptr[ROWS ? b : 0];
+  if (pos < 0 || pos >= S_max) return;
+  const int last = pos / AD_CHUNK;   // < n_chunks: pos < S_max
+  const float* slot = ws + (long)bh * n_chunks * AD_SLOT;
+  float M = -INFINITY;
+  for (int ch = t; ch <= last; ch += WAVE) M = fmaxf(M, slot[(long)ch * AD_SLOT]);
+  M = wave_max_dpp(M);   // every lane gets the same value; a max does not depend on the order
+  float wgt = __expf(slot[0] - M);
+  float L = slot[1] * wgt, acc = slot[2 + t] * wgt;
+  // eight chunks' loads in flight at a time (a load per iteration would pay its latency pos / 128
+  // times in a row); the fold itself stays in increasing chunk order.  A block's tail past
+  // ``last`` re-reads slot ``last`` and is not folded.
+  for (int c0 = 1; c0 <= last; c0 += AD_CB) {
+    float pm[AD_CB], pl[AD_CB], po[AD_CB];
+#pragma unroll
+    for (int k = 0; k < AD_CB; ++k) {
+      const float* s = slot + (long)min(c0 + k, last) * AD_SLOT;
+      pm[k] = s[0];
+      pl[k] = s[1];
+      po[k] = s[2 + t];
+    }
+#pragma unroll
+    for (int k = 0; k < AD_CB; ++k) {
+      if (c0 + k <= last) {
+        wgt = __expf(pm[k] - M);
+        L += pl[k] * wgt;
+        acc += po[k] * wgt;
+      }
+    }
+  }
+  o[((long)b * H + h) * AD_DH + t] = f2bf(acc * (1.f / L));
 }
 
 // one thread per 8 columns, as embed_fwd_kernel (same bf16x8_add -> same bits)
@@ -415,9 +493,9 @@ static int attn_decode_launch(const void* qkv, void* k_cache, void* v_cache, voi
   if (!qkv || !k_cache || !v_cache || !o || !pos) return -2;
   if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
   if (B == 0) return 0;
-  hipLaunchKernelGGL(attn_decode_kernel<ROWS>, dim3(B * H), dim3(256), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL((attn_decode_kernel<ROWS, false>), dim3(B * H), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache),
-                     static_cast<bf16_t*>(o), pos, H, S_max, scale);
+                     static_cast<bf16_t*>(o), pos, H, S_max, scale, static_cast<float*>(nullptr));
   return HIP_LAUNCH_CHECK();
 }
 
@@ -431,6 +509,44 @@ JDT_API int jdt_attn_decode(const void* qkv, void* k_cache, void* v_cache, void*
 JDT_API int jdt_attn_decode_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H,
                                  int Dh, int S_max, float scale, void* stream) {
   return attn_decode_launch<true>(qkv, k_cache, v_cache, o, pos, B, H, Dh, S_max, scale, stream);
+}
+
+// Split-KV: the split launch, then the combine on the same stream.  Everything is checked
+// before anything is launched; -10: a workspace below B * H * ceil(S_max / 128) * 66 floats.
+template <bool ROWS>
+static int attn_decode_long_launch(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, float* ws,
+                                   long ws_floats, int B, int H, int Dh, int S_max, float scale, void* stream) {
+  if (Dh != AD_DH) return -3;
+  if (S_max < 1 || S_max > AD_LONG_SMAX) return -4;
+  if (B < 0 || H < 1 || (long)B * H > INT_MAX) return -5;
+  if (!qkv || !k_cache || !v_cache || !o || !pos || !ws) return -2;
+  if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
+  const int n_chunks = (S_max + AD_CHUNK - 1) / AD_CHUNK;
+  if (ws_floats < (long)B * H * n_chunks * AD_SLOT) return -10;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL((attn_decode_kernel<ROWS, true>), dim3(B * H, n_chunks), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
+                     static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache), static_cast<bf16_t*>(nullptr), pos,
+                     H, S_max, scale, ws);
+  const int rc = HIP_LAUNCH_CHECK();
+  if (rc) return rc;
+  hipLaunchKernelGGL(attn_decode_combine_kernel<ROWS>, dim3(B * H), dim3(WAVE), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const float*>(ws), static_cast<bf16_t*>(o), pos, H, S_max, n_chunks);
+  return HIP_LAUNCH_CHECK();
+}
+
+// jdt_attn_decode for caches of 1 <= S_max <= 32768 rows: ws is fp32 scratch of ws_floats >=
+// B * H * ceil(S_max / 128) * 66 words (any contents; one slot per workgroup of the split launch)
+JDT_API int jdt_attn_decode_long(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, float* ws,
+                                 long ws_floats, int B, int H, int Dh, int S_max, float scale, void* stream) {
+  return attn_decode_long_launch<false>(qkv, k_cache, v_cache, o, pos, ws, ws_floats, B, H, Dh, S_max, scale, stream);
+}
+
+// as jdt_attn_decode_long with one position per sequence: pos int32[B]
+JDT_API int jdt_attn_decode_long_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos,
+                                      float* ws, long ws_floats, int B, int H, int Dh, int S_max, float scale,
+                                      void* stream) {
+  return attn_decode_long_launch<true>(qkv, k_cache, v_cache, o, pos, ws, ws_floats, B, H, Dh, S_max, scale, stream);
 }
 
 template <bool ROWS>

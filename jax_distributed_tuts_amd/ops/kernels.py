@@ -1011,7 +1011,27 @@ def colsum_(x, out):
 # sequence, and the sampler also takes ``end`` int32[B] (one past the last token index a row may
 # hold); a row out of range is a no-op on its own.
 AD_HEAD_DIM, AD_MAX_ROWS = 64, 128   # envelope of jdt_attn_decode (csrc/attn_decode.hip AD_DH, AD_SMAX)
+# split-KV (jdt_attn_decode_long): keys per workgroup, the longest cache, fp32 words of a partial
+# (csrc/attn_decode.hip AD_CHUNK, AD_LONG_SMAX, AD_SLOT)
+AD_CHUNK_ROWS, AD_LONG_MAX_ROWS, AD_SLOT_FLOATS = 128, 32768, 66
 _SAMPLE_TICKET: dict = {}
+_AD_WS: dict = {}
+
+
+def attention_decode_ws_floats(B: int, H: int, S_max: int) -> int:
+    """fp32 words of the split-KV workspace: one partial per (batch, head, 128-key chunk)."""
+    return B * H * ((S_max + AD_CHUNK_ROWS - 1) // AD_CHUNK_ROWS) * AD_SLOT_FLOATS
+
+
+def _decode_workspace(device, n: int) -> torch.Tensor:
+    """Per-device split-KV scratch of >= n floats (any contents: the combine reads only the slots
+    the split launch of the same call wrote).  An outgrown buffer stays allocated: a captured
+    step may still hold its address."""
+    key = str(device)
+    held = _AD_WS.setdefault(key, [])
+    if not held or held[-1].numel() < n:
+        held.append(torch.empty(n, dtype=torch.float32, device=device))
+    return held[-1]
 
 
 def _per_row(pos: torch.Tensor, B: int) -> bool:
@@ -1043,15 +1063,19 @@ def _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out):
 
 
 def attention_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, H: int,
-                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One query token per sequence against a KV cache.  ``qkv`` [B, 3*H*Dh] bf16 (the decode
     step's QKV projection, q | k | v as in training), ``k_cache`` / ``v_cache`` [B, H, S_max, Dh]
     bf16 (one layer), ``pos`` int32[1] (shared) or int32[B] (per row) -> o [B, H*Dh] bf16.
     Appends the token's k / v rows at row ``pos``, then attends over rows 0..pos (softmax
     statistics fp32, p rounded to bf16 before P.V, fp32 accumulate).  A position outside
     ``[0, S_max)``: nothing is written for that row (shared: for any row), ``out`` keeps its
-    contents.  GPU, Dh = 64 and S_max <= 128: csrc/attn_decode.hip; other GPU shapes run the
-    composed torch path (which syncs on ``pos``)."""
+    contents.  GPU and Dh = 64 (csrc/attn_decode.hip): S_max <= 128 is one launch; 128 < S_max <=
+    32768 is the split-KV pair of launches (one workgroup per 128-key chunk leaves a partial in
+    ``ws``, a combine folds them), which reads ``pos`` on the device like the first.  ``ws``: fp32
+    scratch of >= ``attention_decode_ws_floats(B, H, S_max)`` words with any contents (``None``: a
+    per-device buffer); the other paths ignore it.  Other GPU shapes run the composed torch path
+    (which syncs on ``pos``), as CPU tensors do."""
     B, d3 = qkv.shape
     d = d3 // 3
     Dh = d // H
@@ -1060,13 +1084,22 @@ def attention_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     S_max = k_cache.shape[2]
     if out is None:
         out = torch.zeros(B, d, dtype=torch.bfloat16, device=qkv.device)
-    if not _is_gpu(qkv) or Dh != AD_HEAD_DIM or S_max > AD_MAX_ROWS:
+    if not _is_gpu(qkv) or Dh != AD_HEAD_DIM or S_max > AD_LONG_MAX_ROWS:
         return _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out)
     for t in (qkv, k_cache, v_cache, out):
         assert t.is_contiguous() and t.dtype == torch.bfloat16
-    name = "jdt_attn_decode_rows" if rows else "jdt_attn_decode"
-    rc = getattr(_lib.lib(), name)(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos), B, H, Dh, S_max,
-                                   float(1.0 / (Dh ** 0.5)), _lib.stream_ptr())
+    if S_max <= AD_MAX_ROWS:
+        name = "jdt_attn_decode_rows" if rows else "jdt_attn_decode"
+        rc = getattr(_lib.lib(), name)(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos), B, H, Dh,
+                                       S_max, float(1.0 / (Dh ** 0.5)), _lib.stream_ptr())
+        _lib.check(rc, name)
+        return out
+    if ws is None:
+        ws = _decode_workspace(qkv.device, attention_decode_ws_floats(B, H, S_max))
+    assert ws.is_contiguous() and ws.dtype == torch.float32 and ws.device == qkv.device
+    name = "jdt_attn_decode_long_rows" if rows else "jdt_attn_decode_long"
+    rc = getattr(_lib.lib(), name)(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos), _ptr(ws),
+                                   ws.numel(), B, H, Dh, S_max, float(1.0 / (Dh ** 0.5)), _lib.stream_ptr())
     _lib.check(rc, name)
     return out
 

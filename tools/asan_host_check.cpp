@@ -40,6 +40,10 @@ int jdt_sample(const void* logits, long ld, int B, int V, float temperature, uns
                unsigned stream_id, int* tokens, int S_max, int* pos, unsigned* ticket, void* stream);
 int jdt_attn_decode_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H, int Dh,
                          int S_max, float scale, void* stream);
+int jdt_attn_decode_long(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, float* ws,
+                         long ws_floats, int B, int H, int Dh, int S_max, float scale, void* stream);
+int jdt_attn_decode_long_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, float* ws,
+                              long ws_floats, int B, int H, int Dh, int S_max, float scale, void* stream);
 int jdt_embed_decode_rows(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos, int B,
                           int S_max, int d, int vocab, void* stream);
 int jdt_sample_filtered(const void* logits, long ld, int B, int V, float temperature, unsigned long long seed,
@@ -148,6 +152,32 @@ int main() {
          "sample_rows rejects a null pos");
   EXPECT(jdt_sample_rows(buf, 8, 0, 8, 1.f, 0, 0, ip, 128, ip, ip, 3, 50, .9f, nullptr) == 0,
          "sample_rows B = 0 is a no-op");
+  // split-KV launchers: the same envelope up to 32768 rows, plus the workspace (1 x 2 x 3 chunks x 66 floats)
+  float* fp = reinterpret_cast<float*>(buf);
+  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, fp, 396, 1, 2, 32, 320, .125f, nullptr) == -3,
+         "attn_decode_long rejects head dim 32");
+  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, fp, 396, 1, 2, 64, 0, .125f, nullptr) == -4,
+         "attn_decode_long rejects S_max 0");
+  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, fp, 1L << 30, 1, 2, 64, 32769, .125f, nullptr) == -4,
+         "attn_decode_long rejects S_max 32769");
+  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, nullptr, 396, 1, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_decode_long rejects a null ws");
+  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, fp, 395, 1, 2, 64, 320, .125f, nullptr) == -10,
+         "attn_decode_long rejects a short ws");
+  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, fp, 0, 0, 2, 64, 320, .125f, nullptr) == 0,
+         "attn_decode_long B = 0 is a no-op");
+  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, fp, 396, 1, 2, 32, 320, .125f, nullptr) == -3,
+         "attn_decode_long_rows rejects head dim 32");
+  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, fp, 396, 1, 2, 64, 0, .125f, nullptr) == -4,
+         "attn_decode_long_rows rejects S_max 0");
+  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, fp, 1L << 30, 1, 2, 64, 32769, .125f, nullptr) == -4,
+         "attn_decode_long_rows rejects S_max 32769");
+  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, nullptr, 396, 1, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_decode_long_rows rejects a null ws");
+  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, fp, 395, 1, 2, 64, 320, .125f, nullptr) == -10,
+         "attn_decode_long_rows rejects a short ws");
+  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, fp, 0, 0, 2, 64, 320, .125f, nullptr) == 0,
+         "attn_decode_long_rows B = 0 is a no-op");
   std::printf("asan host check: %d failure(s)\n", failures);
   return failures ? 1 : 0;
 }

@@ -2,10 +2,13 @@
 default TransformerConfig at B = 1 and B = 16: us per decode step and tokens/s, launched
 eagerly against one captured step replayed per token, plus the kernel-launcher calls per step.
 
-    python tools/bench_generate.py [--steps 100] [--temperature 0.0] [--ragged]
+    python tools/bench_generate.py [--steps 100] [--temperature 0.0] [--ragged] [--seq-len N] [--prompt-len P]
 
 Each figure: ``--steps`` decode steps after a 16-token prefill, timed with events around the
-whole loop (prefill excluded), median of 5 runs.  ``--ragged`` adds, at B = 16 and a sampling
+whole loop (prefill excluded), median of 5 runs.  ``--seq-len N`` > 128 builds the LM with an
+N-row cache and prefills ``N - steps - 1`` tokens, so the timed steps attend at depth (split-KV
+decode attention); ``--prompt-len`` overrides that, e.g. 16 for a shallow position in a deep
+cache, and ``--batch`` the batch sizes.  ``--ragged`` adds, at B = 16 and a sampling
 temperature (``--temperature``, or 0.8 when that is 0): the uniform batch with the top-k /
 top-p sampler (k = 50, p = 0.9), and a ragged batch (prompt lengths 1..16, per-row positions)
 with the plain and with the filtered sampler.
@@ -73,13 +76,21 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--ragged", action="store_true", help="extra lines: top-k / top-p and a ragged B = 16 batch")
+    ap.add_argument("--seq-len", type=int, default=128, help="cache rows; > 128: the prompt is seq_len - steps - 1")
+    ap.add_argument("--prompt-len", type=int, default=None, help="override the prompt length")
+    ap.add_argument("--batch", default="1,16", help="comma-separated batch sizes of the main lines")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
-    cfg = TransformerConfig()
-    assert PROMPT + a.steps <= cfg.seq_len
+    cfg = TransformerConfig(seq_len=a.seq_len)
+    global PROMPT
+    if a.prompt_len is not None:
+        PROMPT = a.prompt_len
+    elif a.seq_len > 128:
+        PROMPT = a.seq_len - a.steps - 1
+    assert PROMPT >= 1 and PROMPT + a.steps <= cfg.seq_len
     model = TransformerLM(cfg)
     P = FlatParams(model.param_specs(), device=dev).init_(0)
-    for B in (1, 16):
+    for B in (int(v) for v in a.batch.split(",")):
         gen = Generator(model, P, B, dev)
         prompt = torch.randint(0, cfg.vocab_size, (B, PROMPT), generator=torch.Generator().manual_seed(1))
         prompt = prompt.to(torch.int32).to(dev)
@@ -89,7 +100,9 @@ def main():
         reset()
         calls = launches_per_step(gen)
         t_e = timed(gen.step, reset, a.steps)
-        line = (f"generate B={B:2d} T={a.temperature}: eager {t_e:7.1f} us/step ({B / t_e * 1e6:9.0f} tokens/s)")
+        depth = f" S={a.seq_len} P={PROMPT}" if a.seq_len != 128 or a.prompt_len is not None else ""
+        line = (f"generate B={B:2d} T={a.temperature}{depth}: eager {t_e:7.1f} us/step "
+                f"({B / t_e * 1e6:9.0f} tokens/s)")
         if graph is not None:
             t_g = timed(graph.replay, reset, a.steps)
             line += f" | captured {t_g:7.1f} us/step ({B / t_g * 1e6:9.0f} tokens/s)"
