@@ -7,6 +7,7 @@ one captured decode step replayed per token).
     python generate.py --restore ckpt_dir                             # weights of a checkpoint
     python generate.py --batch 3 --prompt-lens 5,16,9 --temperature 0.8 --top-k 50 --top-p 0.9 --eos-id 7
     python generate.py --seq-len 1024 --prompt-len 900 --max-new-tokens 100   # a 1024-row KV cache
+    python generate.py --seq-len 1024 --prompt-len 900 --prefill-chunk 256    # chunked prefill into the cache
 
 Runs the HIP kernels on a GPU and the torch reference paths on CPU tensors when none is
 present.  The prompt is the first ``--prompt-len`` tokens of ``lm_batch``'s sequences;
@@ -14,7 +15,8 @@ present.  The prompt is the first ``--prompt-len`` tokens of ``lm_batch``'s sequ
 ``--top-p`` restrict the sampler and ``--eos-id`` ends a sequence at that token.  Each row is
 printed up to its own final length.  ``--seq-len`` builds the LM with that many learned
 positions (default 128); up to 32768 the decode attention stays on the HIP kernels (split-KV
-past 128 cache rows).
+past 128 cache rows).  ``--prefill-chunk N`` fills the cache through the append kernels in slices
+of N prompt rows instead of one pass of the training forward.
 Not covered: beam search, repetition penalties, sequences past ``seq_len``, caches longer than
 32768 rows or head dims other than 64 on the HIP path, multi-GPU or pipeline-split generation.
 """
@@ -48,6 +50,9 @@ def parse_args(argv=None):
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--seq-len", type=int, default=128, help="learned positions == rows of the KV cache")
     ap.add_argument("--eager", action="store_true", help="launch every decode step eagerly (no graph replay)")
+    ap.add_argument("--prefill-chunk", type=int, default=None, metavar="N",
+                    help="chunked prefill: the prompt goes into the cache in slices of N rows "
+                         "(default: one pass of the training forward)")
     return ap.parse_args(argv)
 
 
@@ -77,7 +82,7 @@ def main(args):
     gen = Generator(tr.state.apply_fn, tr.state.params, args.batch, dev)
     sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
     kw = dict(temperature=args.temperature, seed=args.seed, capture=not args.eager, prompt_lens=lens,
-              top_k=args.top_k, top_p=args.top_p, eos_id=args.eos_id)
+              top_k=args.top_k, top_p=args.top_p, eos_id=args.eos_id, prefill_chunk=args.prefill_chunk)
     out = gen.generate(prompt, args.max_new_tokens, **kw)   # first call: allocations and the step capture
     sync()
     t0 = time.perf_counter()

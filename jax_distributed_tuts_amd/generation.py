@@ -1,5 +1,6 @@
 """Autoregressive generation for the transformer LM: a KV cache, a prefill through the
-training forward and a decode step of one token per sequence.
+training forward or in chunks straight into the cache, and a decode step of one token per
+sequence.
 
 Cache layout: per layer K and V are ``[B, H, seq_len, 64]`` bf16 (a head's keys are
 contiguous 128-byte rows), ``tokens`` is ``int32 [B, seq_len]`` and ``pos`` is a device
@@ -28,10 +29,22 @@ the row's length, which finishes it: its later steps re-process the same token (
 bits) and sample nothing, so the captured step still replays without host bookkeeping.
 The sampler can also be restricted to the top-k / top-p set (``ops.kernels.sample_tokens``).
 
+Appending to the cache: ``advance`` pushes a block of tokens already in ``tokens`` through the
+blocks in slices of at most ``chunk`` rows -- ``embed_append``, then ``TransformerLM.append_chunk``
+with ``ops.kernels.attention_append`` (csrc/attn_append.hip: causal attention of C new query
+rows against the cache in the cache's own layout, one launch per layer) -- with no backward
+cache and no logits it does not need.  ``prefill(prompt, chunk=c)`` (``generate(...,
+prefill_chunk=c)``) fills the cache that way instead of through the training forward, and leaves
+the same position.  ``extend(tokens)`` appends to a live cache: a second turn after a generation,
+teacher forcing a block of tokens, or scoring a continuation (``logits=True``).  The bits a
+token's attention output gets do not depend on how the tokens were cut into calls or slices.
+
 Out of scope: beam search, repetition penalties, sequences longer than ``seq_len`` (the
 learned positions end there), multi-GPU or pipeline-split generation, paged or compacted
-caches, chunked prefill into the cache, removing finished rows from the batch, and head dims
-other than 64 or caches past 32768 rows on the HIP path.
+caches, ``generate()`` continuing a live cache, a split-KV append kernel (an append workgroup
+walks the whole cache above its query tile), removing finished rows from the batch, and head
+dims other than 64 or caches past 32768 rows on the HIP path.  Chunked prefill is opt-in: the
+default ``prefill`` is still the training forward.
 """
 from __future__ import annotations
 
@@ -94,13 +107,22 @@ class Generator:
         self.lengths: Optional[torch.Tensor] = None  # int32 [B]: the final lengths of the last generate
         self.prefill_rows = 0                        # rows per sequence the last prefill's forward ran over
         self._prefill_models: dict = {}              # rows -> the model at that seq_len (same parameters)
+        self._chunk_bufs: dict = {}                  # chunk size -> advance's embedded rows [B * chunk, d_model]
+        self._live = False                           # a prefill has run: extend may append
         # (temperature, seed) -> (graph, its logits); any other sampler setting or the
         # per-row mode: (temperature, seed, top_k, top_p, eos_id, per_row)
         self._graphs: dict = {}
 
     # ------------------------------------------------------------------ prefill
-    def prefill(self, prompt: torch.Tensor, prompt_lens: Optional[torch.Tensor] = None):
+    def prefill(self, prompt: torch.Tensor, prompt_lens: Optional[torch.Tensor] = None, *,
+                chunk: Optional[int] = None):
         """``prompt`` int [B, P], 1 <= P <= seq_len: fills cache rows < P and sets pos = P - 1.
+
+        ``chunk`` (>= 1): chunked prefill -- instead of the training forward, the first P - 1
+        tokens (per row: len_b - 1) go through ``advance`` in slices of at most ``chunk`` rows
+        straight into the cache: no backward cache, no logits, no permute-copies.  It fills cache
+        rows < P - 1 (the decode step writes row P - 1 itself), leaves the same position and
+        leaves ``prefill_rows`` at 0.  ``None``: the path described below.
 
         ``prompt_lens`` (int [B], each in 1..P): ``prompt`` is right-padded, tokens at or past
         a row's length are ignored, and the per-row state becomes live: ``pos_rows[b] =
@@ -111,6 +133,8 @@ class Generator:
         128 (at most ``seq_len``) rows per sequence: a model of that ``seq_len`` on the same
         parameters (the embedding reads only the first ``prefill_rows`` rows of ``wpe``)."""
         c = self.model.cfg
+        if chunk is not None and int(chunk) < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
         if prompt.dim() != 2 or prompt.shape[0] != self.batch or not 1 <= prompt.shape[1] <= c.seq_len:
             raise ValueError(f"prompt must be [{self.batch}, 1..{c.seq_len}], got {tuple(prompt.shape)}")
         B, Pn, H, Dh = self.batch, prompt.shape[1], c.n_heads, c.d_model // c.n_heads
@@ -127,6 +151,15 @@ class Generator:
         kv = self.kv
         kv.tokens.zero_()
         kv.tokens[:, :Pn] = prompt
+        self._live = True
+        if chunk is not None:
+            self.prefill_rows = 0
+            kv.per_row = lens is not None
+            kv.live_pos.zero_()
+            if kv.per_row:
+                kv.end.fill_(c.seq_len)
+            self.advance(lens.cpu() - 1 if kv.per_row else Pn - 1, chunk=int(chunk))
+            return
         model, Sp = self.model, c.seq_len
         if c.seq_len > K.AD_CHUNK_ROWS:
             Sp = min(-(-Pn // K.AD_CHUNK_ROWS) * K.AD_CHUNK_ROWS, c.seq_len)
@@ -146,6 +179,106 @@ class Generator:
             kv.end.fill_(c.seq_len)
         else:
             kv.pos.fill_(Pn - 1)
+
+    # ------------------------------------------------------------------ append
+    def advance(self, n, *, chunk: int, logits: bool = False) -> Optional[torch.Tensor]:
+        """Process the ``n`` tokens already in ``kv.tokens`` at positions pos..pos+n-1 (their k / v
+        go to the cache) and add ``n`` to the position, in slices of at most ``chunk`` rows:
+        ``embed_append``, ``TransformerLM.append_chunk``, ``live_pos += slice count``.  ``n``: an
+        int or, per-row mode only, an int tensor [B] (slice j of row b then holds
+        ``clamp(n_b - j * chunk, 0, chunk)`` tokens).  The position is never read on the host: the
+        counts come from ``n``, and the caller answers for ``pos + n <= seq_len`` (a slice that would
+        pass the end of the cache writes nothing, but the position still advances).
+
+        ``logits=True``: returns the logits [B, vocab] of each row's last processed token (a row
+        with nothing to process: of a zero vector); their block outputs are gathered before
+        ``ln_f`` / the head, so the head runs at M = B."""
+        kv, P, c, B = self.kv, self.P, self.model.cfg, self.batch
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        if isinstance(n, torch.Tensor) and n.dim() > 0:
+            if not kv.per_row:
+                raise ValueError("a per-row n needs the per-row cache state (prefill with prompt_lens)")
+            nb = [int(v) for v in n.tolist()]
+            if len(nb) != B:
+                raise ValueError(f"n must be an int or {B} integers, got {nb}")
+        else:
+            nb = [int(n)] * B
+        if min(nb) < 0:
+            raise ValueError(f"n must be >= 0, got {nb}")
+        uniform = min(nb) == max(nb)
+        pos = kv.live_pos
+        x = self._chunk_bufs.get(chunk)
+        if x is None:   # once per chunk size, zero-initialised: rows past a count stay finite
+            x = self._chunk_bufs[chunk] = torch.zeros(B * chunk, c.d_model, dtype=torch.bfloat16, device=self.device)
+        last = torch.zeros(B, c.d_model, dtype=torch.bfloat16, device=self.device) if logits else None
+        for lo in range(0, max(nb), chunk):
+            C = min(chunk, max(nb) - lo)
+            cnt = [min(max(v - lo, 0), C) for v in nb]
+            count = None if uniform else torch.tensor(cnt, dtype=torch.int32, device=self.device)
+            xs = x[:B * C]
+            K.embed_append(kv.tokens, P.s("embed/wte"), P.s("embed/wpe"), pos, C, count=count, out=xs)
+            h = self.model.append_chunk(P, kv, xs, C, count=count)
+            if logits:
+                ends = [(b, b * C + v - lo - 1) for b, v in enumerate(nb) if lo < v <= lo + C]
+                if ends:
+                    dst = torch.tensor([b for b, _ in ends], device=self.device)
+                    src = torch.tensor([r for _, r in ends], device=self.device)
+                    last[dst] = h[src]
+            if uniform:
+                pos.add_(C)
+            else:
+                pos.add_(count)
+        if logits:
+            self.logits = self.model.lm_head(P, last)
+            return self.logits
+        return None
+
+    def extend(self, tokens: torch.Tensor, lens: Optional[torch.Tensor] = None, *, chunk: int = 64,
+               logits: bool = False) -> Optional[torch.Tensor]:
+        """Append ``tokens`` int [B, n] to a live cache (a second turn after a generation, teacher
+        forcing a block, scoring a continuation): they are written at pos + 1 .. pos + n and
+        ``advance(n)`` processes the n tokens from pos on, so ``pos`` again indexes the last, not yet
+        processed, token and ``step`` / ``extend`` can follow.  ``lens`` (int [B], each in 0..n;
+        per-row caches only): ``tokens`` is right-padded and row b appends its first ``lens[b]``
+        tokens.  In per-row mode every row's ``end`` is set back to ``seq_len``.  ``logits=True``:
+        the logits [B, vocab] of each row's last processed token, the one at the new pos - 1 (they
+        predict the last token given).  Reads the position on the host once, to check the bounds.
+
+        Raises ``ValueError`` before any prefill, for ``lens`` on a shared-position cache and when a
+        row would pass ``seq_len``."""
+        kv, c, B = self.kv, self.model.cfg, self.batch
+        if not self._live:
+            raise ValueError("extend needs a live cache: call prefill (or generate) first")
+        if int(chunk) < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        if lens is not None and not kv.per_row:
+            raise ValueError("lens needs the per-row cache state (prefill with prompt_lens)")
+        if tokens.dim() != 2 or tokens.shape[0] != B:
+            raise ValueError(f"tokens must be [{B}, n], got {tuple(tokens.shape)}")
+        n = tokens.shape[1]
+        tokens = tokens.to(device=self.device, dtype=torch.int32)
+        if lens is None:
+            nb = [n] * B
+        else:
+            lt = torch.as_tensor(lens)
+            if lt.shape != (B,) or lt.dtype.is_floating_point or int(lt.min()) < 0 or int(lt.max()) > n:
+                raise ValueError(f"lens must be {B} integers in 0..{n}, got {lt.tolist()}")
+            nb = [int(v) for v in lt.tolist()]
+            tokens = tokens * (torch.arange(n, device=self.device)[None] < lt.to(self.device)[:, None])
+        if n and (int(tokens.min()) < 0 or int(tokens.max()) >= c.vocab_size):
+            raise ValueError(f"token outside [0, {c.vocab_size})")
+        pv = kv.live_pos.tolist() if kv.per_row else kv.live_pos.tolist() * B
+        for b, (p, v) in enumerate(zip(pv, nb)):
+            if p < 0 or p + v > c.seq_len - 1:
+                raise ValueError(f"row {b}: position {p} + {v} new tokens passes seq_len {c.seq_len} "
+                                 f"(the learned positions end there)")
+        for b, (p, v) in enumerate(zip(pv, nb)):
+            kv.tokens[b, p + 1:p + 1 + v] = tokens[b, :v]
+        if kv.per_row:
+            kv.end.fill_(c.seq_len)
+        return self.advance(torch.tensor(nb) if kv.per_row else n, chunk=chunk, logits=logits)
 
     # ------------------------------------------------------------------ one step
     def step(self, sample: bool = True) -> torch.Tensor:
@@ -197,13 +330,15 @@ class Generator:
     # ------------------------------------------------------------------ generate
     def generate(self, prompt: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, seed: int = 0,
                  capture: bool = True, *, prompt_lens: Optional[torch.Tensor] = None, top_k: int = 0,
-                 top_p: float = 1.0, eos_id: Optional[int] = None, pad_id: int = 0) -> torch.Tensor:
+                 top_p: float = 1.0, eos_id: Optional[int] = None, pad_id: int = 0,
+                 prefill_chunk: Optional[int] = None) -> torch.Tensor:
         """``prompt`` int [B, P] -> int32 [B, P + max_new_tokens] (the prompt, then the new
         tokens).  ``temperature == 0``: greedy; otherwise softmax(logits / T) sampling from
         Philox stream ``seed``, restricted to the ``top_k`` largest logits (0: off) and, of
         those, the smallest head of probability mass >= ``top_p`` (1.0: off); ties at a
         threshold are kept.  ``capture`` (GPU only): the decode step is captured into a graph
-        once per sampler setting and replayed per token.
+        once per sampler setting and replayed per token.  ``prefill_chunk``: ``prefill``'s ``chunk``
+        (chunked prefill into the cache; ``None``: through the training forward).
 
         ``prompt_lens`` (int [B], each in 1..P; ``prompt`` right-padded) or ``eos_id`` select the
         per-row mode: row b starts at its own length len_b and may grow to len_b +
@@ -224,7 +359,7 @@ class Generator:
             if max_new_tokens < 0 or Pn + max_new_tokens > c.seq_len:
                 raise ValueError(f"prompt length {Pn} + max_new_tokens {max_new_tokens} exceeds seq_len "
                                  f"{c.seq_len} (the learned positions end there)")
-            self.prefill(prompt)
+            self.prefill(prompt, chunk=prefill_chunk)
             for _ in range(max_new_tokens):
                 run()
             self.lengths = torch.full((self.batch,), Pn + max_new_tokens, dtype=torch.int32, device=self.device)
@@ -238,7 +373,7 @@ class Generator:
         if max_new_tokens < 0 or longest + max_new_tokens > c.seq_len:
             raise ValueError(f"longest prompt {longest} + max_new_tokens {max_new_tokens} exceeds seq_len "
                              f"{c.seq_len} (the learned positions end there)")
-        self.prefill(prompt, lens)
+        self.prefill(prompt, lens, chunk=prefill_chunk)
         kv = self.kv
         kv.end.copy_(kv.pos_rows + 1 + max_new_tokens)
         for i in range(1, max_new_tokens + 1):

@@ -241,6 +241,44 @@ class TransformerLM:
                                     bias=P.s("head/bias"))
         return logits
 
+    def append_chunk(self, P: FlatParams, kv, x: torch.Tensor, C: int, count: Optional[torch.Tensor] = None,
+                     head: bool = False) -> torch.Tensor:
+        """``C`` tokens per sequence through the blocks, in inference mode with no ``_Cache``: the
+        block loop of ``decode_step`` at M = B*C with ``attention_append`` (appends the tokens' k / v
+        to layer l's cache at rows pos..pos+C-1, attends causally over rows 0..pos+i) in the place of
+        ``attention_decode``.  ``x`` [B*C, d_model] bf16: row b*C + i is the embedded token at
+        position pos + i (``ops.kernels.embed_append``); ``count`` int32[B] (per-row cache only): the
+        tokens sequence b really appends, rows past it are computed on whatever ``x`` holds and mean
+        nothing.  The position is the cache's live tensor and is only read.  ``head=False`` skips
+        ``ln_f`` and the head entirely and returns the last block's output [B*C, d_model];
+        ``head=True`` returns the logits [B*C, vocab] (``lm_head``)."""
+        if not (self.has_embed and self.has_head):
+            raise ValueError("append_chunk needs the full model (embedding and head): "
+                             "pipeline-split stages cannot generate")
+        c = self.cfg
+        pos = kv.pos_rows if getattr(kv, "per_row", False) else kv.pos
+        h = x
+        for l in self.layers:
+            b = f"block_{l}"
+            qkv, _, _, _ = K.ln_gemm(h, P.p(f"{b}/ln1/scale"), P.p(f"{b}/ln1/bias"), P.s(f"{b}/attn/qkv/kernel"),
+                                     eps=c.ln_eps, bias=P.s(f"{b}/attn/qkv/bias"))
+            # per-row counts: rows past a sequence's count keep the zeros (finite inputs for the GEMMs below)
+            mk = torch.empty if count is None else torch.zeros
+            o = mk(h.shape[0], c.d_model, dtype=torch.bfloat16, device=h.device)
+            K.attention_append(qkv, kv.k[l], kv.v[l], pos, c.n_heads, C, count=count, out=o)
+            x2 = K.gemm(o, P.s(f"{b}/attn/out/kernel"), bias=P.s(f"{b}/attn/out/bias"), resid=h)
+            z1 = torch.empty(x2.shape[0], c.d_ff, dtype=torch.bfloat16, device=x2.device)
+            u, _, _, _ = K.ln_gemm(x2, P.p(f"{b}/ln2/scale"), P.p(f"{b}/ln2/bias"), P.s(f"{b}/mlp/fc1/kernel"),
+                                   eps=c.ln_eps, bias=P.s(f"{b}/mlp/fc1/bias"), act="gelu", z_out=z1)
+            h = K.gemm(u, P.s(f"{b}/mlp/fc2/kernel"), bias=P.s(f"{b}/mlp/fc2/bias"), resid=x2)
+        return self.lm_head(P, h) if head else h
+
+    def lm_head(self, P: FlatParams, h: torch.Tensor) -> torch.Tensor:
+        """``ln_f`` and the head on block outputs ``h`` [M, d_model] bf16 -> logits [M, vocab]."""
+        logits, _, _, _ = K.ln_gemm(h, P.p("ln_f/scale"), P.p("ln_f/bias"), P.s("head/kernel"), eps=self.cfg.ln_eps,
+                                    bias=P.s("head/bias"))
+        return logits
+
     # ------------------------------------------------------------------ backward
     def backward(self, P: FlatParams, cache: _Cache, dout: torch.Tensor, *, dout_is_dz: bool = True,
                  need_dx: bool = False, on_ready=None, wgrad=None, opt=None, after=None) -> Optional[torch.Tensor]:

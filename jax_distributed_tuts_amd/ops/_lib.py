@@ -130,6 +130,17 @@ _SIGS = {
                                      c_int, c_int, c_float, c_void_p]),
     "jdt_attn_decode_long_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int,
                                           c_int, c_int, c_int, c_float, c_void_p]),
+    # csrc/attn_append.hip, C new tokens per sequence: (qkv, k_cache, v_cache, o, pos, B, C, H, Dh, S_max, scale,
+    # stream); per row: (..., pos, count, B, ...)
+    "jdt_attn_append": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                c_float, c_void_p]),
+    "jdt_attn_append_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                     c_int, c_int, c_float, c_void_p]),
+    # (tokens, wte, wpe, out, pos, B, C, S_max, d, vocab, stream); per row: (..., pos, count, B, ...)
+    "jdt_embed_append": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                 c_void_p]),
+    "jdt_embed_append_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_int, c_int, c_void_p]),
     # (logits, ld, B, V, temperature, seed, stream_id, tokens, S_max, pos, ticket, top_k, top_p, stream)
     "jdt_sample_filtered": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_ulonglong, ctypes.c_uint, c_void_p,
                                     c_int, c_void_p, c_void_p, c_int, c_float, c_void_p]),

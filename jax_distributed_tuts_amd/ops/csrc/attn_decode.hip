@@ -23,6 +23,7 @@
 //               workgroup leaving an unnormalised partial in a workspace slot, then a second
 //               launch that folds the partials -- the kernel boundary is the hand-off.
 // embed_decode: x[b] = wte[tokens[b, pos]] + wpe[pos]   (the bits embed_fwd_kernel stores)
+// embed_append: the same for a block of C tokens per sequence from pos on (attn_append.hip's input)
 // sample:       argmax (temperature 0) or inverse-CDF sampling of softmax(logits / T),
 //               optionally restricted to the top-k / top-p set (FILT = true)
 #include "common.h"
@@ -236,6 +237,31 @@ __global__ void __launch_bounds__(256) embed_decode_kernel(const int* __restrict
   const u32x4 a = *reinterpret_cast<const u32x4*>(wte + (long)v * d + c);
   const u32x4 p = *reinterpret_cast<const u32x4*>(wpe + (long)pos * d + c);
   *reinterpret_cast<u32x4*>(out + (long)b * d + c) = bf16x8_add(a, p);
+}
+
+// embed_decode for a block of C tokens per sequence (the input of attn_append.hip's step):
+// out[b*C + i] = wte[tokens[b, p + i]] + wpe[p + i] for i < n, with p = pos[b] and n = count[b]
+// (shared position: pos[0] and n = C).  Rows i >= n keep their contents; p < 0, p + n > S_max or
+// n outside 0..C: nothing is written for the sequence.  One thread per 8 columns, as above.
+template <bool ROWS>
+__global__ void __launch_bounds__(256) embed_append_kernel(const int* __restrict__ tokens,
+                                                          const bf16_t* __restrict__ wte,
+                                                          const bf16_t* __restrict__ wpe, bf16_t* __restrict__ out,
+                                                          const int* __restrict__ pos_ptr,
+                                                          const int* __restrict__ count, int B, int C, int S_max,
+                                                          int d, int vocab) {
+  const int per_row = d / 8;
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long)B * C * per_row) return;
+  const int row = (int)(t / per_row), c = (int)(t % per_row) * 8;   // row = b * C + i < B * C <= INT_MAX
+  const int b = row / C, i = row % C;
+  const int p = pos_ptr[ROWS ? b : 0], n = ROWS ? count[b] : C;
+  if (n < 0 || n > C || p < 0 || p > S_max - n || i >= n) return;
+  const int v = tokens[(long)b * S_max + p + i];
+  if ((unsigned)v >= (unsigned)vocab) return;   // never read outside the table
+  const u32x4 a = *reinterpret_cast<const u32x4*>(wte + (long)v * d + c);
+  const u32x4 e = *reinterpret_cast<const u32x4*>(wpe + (long)(p + i) * d + c);
+  *reinterpret_cast<u32x4*>(out + (long)row * d + c) = bf16x8_add(a, e);
 }
 
 // 8 logits from column i0 (a multiple of 8) of a row; columns >= V read as -inf
@@ -575,6 +601,36 @@ JDT_API int jdt_embed_decode(const int* tokens, const void* wte, const void* wpe
 JDT_API int jdt_embed_decode_rows(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos,
                                   int B, int S_max, int d, int vocab, void* stream) {
   return embed_decode_launch<true>(tokens, wte, wpe, out, pos, B, S_max, d, vocab, stream);
+}
+
+// -11: C outside 1..1024 (the envelope of jdt_attn_append)
+template <bool ROWS>
+static int embed_append_launch(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos,
+                               const int* count, int B, int C, int S_max, int d, int vocab, void* stream) {
+  if (d < 8 || d % 8) return -3;
+  if (C < 1 || C > 1024) return -11;
+  if (S_max < 1 || vocab < 1 || B < 0 || (long)B * C > INT_MAX) return -5;
+  if (!tokens || !wte || !wpe || !out || !pos || (ROWS && !count)) return -2;
+  if (misaligned16(wte) || misaligned16(wpe) || misaligned16(out)) return -6;
+  if (B == 0) return 0;
+  const long blocks = ((long)B * C * (d / 8) + 255) / 256;
+  if (blocks > INT_MAX) return -5;
+  hipLaunchKernelGGL(embed_append_kernel<ROWS>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     tokens, static_cast<const bf16_t*>(wte), static_cast<const bf16_t*>(wpe),
+                     static_cast<bf16_t*>(out), pos, count, B, C, S_max, d, vocab);
+  return HIP_LAUNCH_CHECK();
+}
+
+// out [B*C, d] bf16: row b*C + i = wte[tokens[b, pos + i]] + wpe[pos + i]; tokens int32 [B, S_max]; pos int32[1]
+JDT_API int jdt_embed_append(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos, int B,
+                             int C, int S_max, int d, int vocab, void* stream) {
+  return embed_append_launch<false>(tokens, wte, wpe, out, pos, nullptr, B, C, S_max, d, vocab, stream);
+}
+
+// one position and one token count (0..C) per sequence: pos int32[B], count int32[B]
+JDT_API int jdt_embed_append_rows(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos,
+                                  const int* count, int B, int C, int S_max, int d, int vocab, void* stream) {
+  return embed_append_launch<true>(tokens, wte, wpe, out, pos, count, B, C, S_max, d, vocab, stream);
 }
 
 // The checks and the launch of the three sampler entry points.  ROWS: ``end`` in the place of

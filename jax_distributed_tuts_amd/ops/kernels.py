@@ -1138,6 +1138,124 @@ def embed_decode(tokens: torch.Tensor, wte: torch.Tensor, wpe: torch.Tensor, pos
     return out
 
 
+# ----------------------------------------------------------------------------- append (C tokens per sequence)
+AP_MAX_ROWS, AP_MAX_CHUNK = 32768, 1024   # envelope of jdt_attn_append (csrc/attn_append.hip AP_SMAX, AP_CMAX)
+
+
+def _append_state(pos: torch.Tensor, count: Optional[torch.Tensor], B: int, C: int):
+    """(per-row?, count as int32[B] or None).  ``count`` needs the per-row position."""
+    rows = _per_row(pos, B)
+    if count is not None:
+        assert rows or B == 1, "count needs the per-row state (pos int32[B])"
+        assert count.dtype == torch.int32 and count.numel() == B and count.device == pos.device
+        rows = True
+    elif rows:
+        count = torch.full((B,), C, dtype=torch.int32, device=pos.device)
+    return rows, count
+
+
+def _append_host_ranges(pos, count, B, C, S_max, rows):
+    """[(b, p, n)] of the sequences that append anything, from a host read of ``pos`` / ``count``
+    with the kernels' range rule: p < 0, p + n > S_max or n outside 0..C drop the sequence (shared
+    position: every sequence)."""
+    pv = pos.tolist() if rows else pos.tolist() * B
+    nv = count.tolist() if rows else [C] * B
+    return [(b, p, n) for b, (p, n) in enumerate(zip(pv, nv)) if 0 < n <= C and 0 <= p <= S_max - n]
+
+
+def _attention_append_torch(qkv, k_cache, v_cache, pos, H, C, count, rows, out):
+    """Composed torch path (any head dim / cache length, any device): reads ``pos`` on the host."""
+    B, _, S_max, Dh = k_cache.shape
+    d = H * Dh
+    q5, o3 = qkv.view(B, C, 3, H, Dh), out.view(B, C, d)
+    for b, p, n in _append_host_ranges(pos, count, B, C, S_max, rows):
+        q, k, v = q5[b, :n].unbind(1)   # [n, H, Dh]
+        k_cache[b, :, p:p + n] = k.permute(1, 0, 2)
+        v_cache[b, :, p:p + n] = v.permute(1, 0, 2)
+        Kc, Vc = _bf(k_cache[b, :, :p + n].float()), _bf(v_cache[b, :, :p + n].float())
+        s = torch.einsum("ihd,hjd->hij", _bf(q.float()), Kc) * (1.0 / (Dh ** 0.5))
+        key, qabs = torch.arange(p + n, device=s.device), p + torch.arange(n, device=s.device)
+        s = s.masked_fill(key[None, :] > qabs[:, None], float("-inf"))
+        pr = torch.softmax(s, dim=-1).to(torch.bfloat16).float()   # p rounded to bf16 before P.V, as attention_fwd
+        o3[b, :n] = torch.einsum("hij,hjd->ihd", pr, Vc).reshape(n, d).to(torch.bfloat16)
+    return out
+
+
+def attention_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, H: int,
+                     C: int, count: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``C`` new query tokens per sequence against a KV cache (chunked prefill, teacher forcing,
+    scoring a continuation).  ``qkv`` [B*C, 3*H*Dh] bf16 (row b*C + i is token i of sequence b;
+    q | k | v as in training), ``k_cache`` / ``v_cache`` [B, H, S_max, Dh] bf16 (one layer), ``pos``
+    int32[1] (shared) or int32[B] (per row), ``count`` int32[B] (per row only: sequence b appends
+    ``count[b]`` in 0..C tokens; default C) -> o [B*C, H*Dh] bf16.
+
+    For sequence b with p = pos[b] and n = count[b]: cache rows p..p+n-1 receive the tokens' k / v
+    bit for bit and ``o[b*C + i]`` (i < n) is the attention of q_i over keys 0..p+i (softmax
+    statistics fp32, p rounded to bf16 before P.V, fp32 accumulate); rows i >= n of ``out`` keep
+    their contents.  ``p < 0`` or ``p + n > S_max``: nothing is written for that sequence (shared
+    position: for any).  GPU, Dh = 64, S_max <= 32768 and C <= 1024: one launch of
+    csrc/attn_append.hip, which reads ``pos`` / ``count`` on the device; its bits for the token at
+    absolute index t depend only on (q_t, K[0..t], V[0..t]), not on how the tokens were cut into
+    calls.  Other GPU shapes run the composed torch path (which syncs on ``pos``), as CPU tensors do."""
+    T, d3 = qkv.shape
+    d = d3 // 3
+    Dh = d // H
+    B = k_cache.shape[0]
+    assert C >= 1 and T == B * C, "qkv must hold C rows per sequence"
+    assert k_cache.shape == v_cache.shape and k_cache.shape[:2] == (B, H) and k_cache.shape[3] == Dh
+    rows, count = _append_state(pos, count, B, C)
+    S_max = k_cache.shape[2]
+    if out is None:
+        out = torch.zeros(T, d, dtype=torch.bfloat16, device=qkv.device)
+    assert out.shape == (T, d)
+    if not _is_gpu(qkv) or Dh != AD_HEAD_DIM or S_max > AP_MAX_ROWS or C > AP_MAX_CHUNK:
+        return _attention_append_torch(qkv, k_cache, v_cache, pos, H, C, count, rows, out)
+    for t in (qkv, k_cache, v_cache, out):
+        assert t.is_contiguous() and t.dtype == torch.bfloat16
+    scale = float(1.0 / (Dh ** 0.5))
+    if rows:
+        rc = _lib.lib().jdt_attn_append_rows(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos),
+                                             _ptr(count), B, C, H, Dh, S_max, scale, _lib.stream_ptr())
+        _lib.check(rc, "jdt_attn_append_rows")
+    else:
+        rc = _lib.lib().jdt_attn_append(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos), B, C, H, Dh,
+                                        S_max, scale, _lib.stream_ptr())
+        _lib.check(rc, "jdt_attn_append")
+    return out
+
+
+def embed_append(tokens: torch.Tensor, wte: torch.Tensor, wpe: torch.Tensor, pos: torch.Tensor, C: int,
+                 count: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x[b*C + i] = wte[tokens[b, p + i]] + wpe[p + i] for i < n (bf16, the bits ``embed_fwd`` /
+    ``embed_decode`` give those rows) with p = pos[b] and n = count[b]: the state of
+    ``attention_append``.  Rows i >= n of ``out`` [B*C, d] keep their contents, and a sequence with
+    ``p < 0`` or ``p + n > S_max`` writes nothing (shared position: none does)."""
+    B, S_max = tokens.shape
+    d = wte.shape[1]
+    assert tokens.dtype == torch.int32 and wpe.shape[0] >= S_max and wpe.shape[1] == d and C >= 1
+    rows, count = _append_state(pos, count, B, C)
+    if out is None:
+        out = torch.zeros(B * C, d, dtype=torch.bfloat16, device=tokens.device)
+    assert out.shape == (B * C, d)
+    if not _is_gpu(tokens) or C > AP_MAX_CHUNK:
+        o3 = out.view(B, C, d)
+        for b, p, n in _append_host_ranges(pos, count, B, C, S_max, rows):
+            o3[b, :n] = (wte.float()[tokens[b, p:p + n].long()] + wpe.float()[p:p + n]).to(torch.bfloat16)
+        return out
+    for t in (tokens, wte, wpe, out):
+        assert t.is_contiguous()
+    assert wte.dtype == wpe.dtype == out.dtype == torch.bfloat16
+    if rows:
+        rc = _lib.lib().jdt_embed_append_rows(_ptr(tokens), _ptr(wte), _ptr(wpe), _ptr(out), _ptr(pos), _ptr(count),
+                                              B, C, S_max, d, int(wte.shape[0]), _lib.stream_ptr())
+        _lib.check(rc, "jdt_embed_append_rows")
+    else:
+        rc = _lib.lib().jdt_embed_append(_ptr(tokens), _ptr(wte), _ptr(wpe), _ptr(out), _ptr(pos), B, C, S_max, d,
+                                         int(wte.shape[0]), _lib.stream_ptr())
+        _lib.check(rc, "jdt_embed_append")
+    return out
+
+
 def _filter_weights(x: torch.Tensor, w: torch.Tensor, top_k: int, top_p: float) -> torch.Tensor:
     """The sampling weights ``w`` [n, V] fp32 of the logits ``x`` with everything outside the
     top-k / top-p set zeroed.  top-k: tau_k is the k-th largest logit of the row and

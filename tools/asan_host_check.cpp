@@ -52,6 +52,14 @@ int jdt_sample_filtered(const void* logits, long ld, int B, int V, float tempera
 int jdt_sample_rows(const void* logits, long ld, int B, int V, float temperature, unsigned long long seed,
                     unsigned stream_id, int* tokens, int S_max, int* pos, int* end, int eos_id, int top_k, float top_p,
                     void* stream);
+int jdt_attn_append(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int C, int H, int Dh,
+                    int S_max, float scale, void* stream);
+int jdt_attn_append_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, const int* count,
+                         int B, int C, int H, int Dh, int S_max, float scale, void* stream);
+int jdt_embed_append(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos, int B, int C,
+                     int S_max, int d, int vocab, void* stream);
+int jdt_embed_append_rows(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos,
+                          const int* count, int B, int C, int S_max, int d, int vocab, void* stream);
 }
 
 static int failures = 0;
@@ -178,6 +186,49 @@ int main() {
          "attn_decode_long_rows rejects a short ws");
   EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, fp, 0, 0, 2, 64, 320, .125f, nullptr) == 0,
          "attn_decode_long_rows B = 0 is a no-op");
+  // append launchers (attn_append.hip, embed_append): Dh = 64, S_max in 1..32768, C in 1..1024
+  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 1, 64, 2, 32, 320, .125f, nullptr) == -3,
+         "attn_append rejects head dim 32");
+  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 1, 64, 2, 64, 0, .125f, nullptr) == -4, "attn_append rejects S_max 0");
+  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 1, 64, 2, 64, 32769, .125f, nullptr) == -4,
+         "attn_append rejects S_max 32769");
+  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 1, 0, 2, 64, 320, .125f, nullptr) == -11, "attn_append rejects C 0");
+  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 1, 1025, 2, 64, 320, .125f, nullptr) == -11,
+         "attn_append rejects C 1025");
+  EXPECT(jdt_attn_append(buf, buf, nullptr, buf, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_append rejects null");
+  EXPECT(jdt_attn_append(buf, buf + 4, buf, buf, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
+         "attn_append rejects a misaligned cache");
+  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 65536, 64, 1, 64, 320, .125f, nullptr) == -5,
+         "attn_append rejects B * H past the grid");
+  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 0, 64, 2, 64, 320, .125f, nullptr) == 0, "attn_append B = 0 is a no-op");
+  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, ip, ip, 1, 64, 2, 128, 320, .125f, nullptr) == -3,
+         "attn_append_rows rejects head dim 128");
+  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, ip, ip, 1, 64, 2, 64, 32769, .125f, nullptr) == -4,
+         "attn_append_rows rejects S_max 32769");
+  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, ip, ip, 1, 1025, 2, 64, 320, .125f, nullptr) == -11,
+         "attn_append_rows rejects C 1025");
+  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, ip, nullptr, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_append_rows rejects a null count");
+  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, nullptr, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_append_rows rejects a null pos");
+  EXPECT(jdt_attn_append_rows(buf + 4, buf, buf, buf, ip, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
+         "attn_append_rows rejects a misaligned qkv");
+  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, ip, ip, 0, 64, 2, 64, 320, .125f, nullptr) == 0,
+         "attn_append_rows B = 0 is a no-op");
+  EXPECT(jdt_embed_append(ip, buf, buf, buf, ip, 1, 64, 128, 60, 8, nullptr) == -3, "embed_append rejects d % 8");
+  EXPECT(jdt_embed_append(ip, buf, buf, buf, ip, 1, 0, 128, 64, 8, nullptr) == -11, "embed_append rejects C 0");
+  EXPECT(jdt_embed_append(ip, buf, buf, buf, ip, 1, 64, 0, 64, 8, nullptr) == -5, "embed_append rejects S_max 0");
+  EXPECT(jdt_embed_append(ip, buf, buf, nullptr, ip, 1, 64, 128, 64, 8, nullptr) == -2, "embed_append rejects null");
+  EXPECT(jdt_embed_append(ip, buf, buf, buf + 4, ip, 1, 64, 128, 64, 8, nullptr) == -6,
+         "embed_append rejects a misaligned out");
+  EXPECT(jdt_embed_append(ip, buf, buf, buf, ip, 0, 64, 128, 64, 8, nullptr) == 0, "embed_append B = 0 is a no-op");
+  EXPECT(jdt_embed_append_rows(ip, buf, buf, buf, ip, nullptr, 1, 64, 128, 64, 8, nullptr) == -2,
+         "embed_append_rows rejects a null count");
+  EXPECT(jdt_embed_append_rows(ip, buf, buf, buf, ip, ip, 1, 1025, 128, 64, 8, nullptr) == -11,
+         "embed_append_rows rejects C 1025");
+  EXPECT(jdt_embed_append_rows(ip, buf, buf, buf, ip, ip, 0, 64, 128, 64, 8, nullptr) == 0,
+         "embed_append_rows B = 0 is a no-op");
   std::printf("asan host check: %d failure(s)\n", failures);
   return failures ? 1 : 0;
 }

@@ -3,6 +3,7 @@ default TransformerConfig at B = 1 and B = 16: us per decode step and tokens/s, 
 eagerly against one captured step replayed per token, plus the kernel-launcher calls per step.
 
     python tools/bench_generate.py [--steps 100] [--temperature 0.0] [--ragged] [--seq-len N] [--prompt-len P]
+                                   [--prefill-chunk N[,N...]]
 
 Each figure: ``--steps`` decode steps after a 16-token prefill, timed with events around the
 whole loop (prefill excluded), median of 5 runs.  ``--seq-len N`` > 128 builds the LM with an
@@ -11,11 +12,14 @@ decode attention); ``--prompt-len`` overrides that, e.g. 16 for a shallow positi
 cache, and ``--batch`` the batch sizes.  ``--ragged`` adds, at B = 16 and a sampling
 temperature (``--temperature``, or 0.8 when that is 0): the uniform batch with the top-k /
 top-p sampler (k = 50, p = 0.9), and a ragged batch (prompt lengths 1..16, per-row positions)
-with the plain and with the filtered sampler.
+with the plain and with the filtered sampler.  ``--prefill-chunk 64,256,1024`` adds, per batch
+size, the time and the peak memory of one prefill of the same prompt through the training forward
+and through chunked prefill at each chunk size (``prefill_lines``).
 """
 import argparse
 import os
 import sys
+import time
 
 import torch
 
@@ -71,8 +75,41 @@ def timed(run, reset, steps):
     return sorted(ts)[2]
 
 
+def prefill_lines(model, P, B, dev, prompt, chunks, reps=5):
+    """One line per prefill path -- the training forward, then chunked prefill at each chunk size:
+    the time of one ``prefill`` (host clock around a call that ends in a device synchronise,
+    median of ``reps`` after a warm-up call that also makes every allocation and GEMM tile
+    choice) and the peak of ``torch.cuda.max_memory_allocated`` during the timed calls, beside
+    what was allocated before them (parameters, the KV cache and the path's persistent buffers)."""
+    cfg = model.cfg
+    for chunk in [None] + list(chunks):
+        gen = Generator(model, P, B, dev)
+        gen.prefill(prompt, chunk=chunk)
+        torch.cuda.synchronize(dev)
+        held = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        ts = []
+        for _ in range(reps):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            gen.prefill(prompt, chunk=chunk)
+            torch.cuda.synchronize(dev)
+            ts.append((time.perf_counter() - t0) * 1e3)
+        peak = torch.cuda.max_memory_allocated(dev)
+        ts.sort()
+        path = "training forward" if chunk is None else f"chunk {chunk:4d}"
+        print(f"prefill  B={B:2d} S={cfg.seq_len} P={prompt.shape[1]} {path:>16}: {ts[len(ts) // 2]:9.2f} ms "
+              f"(min {ts[0]:.2f}, max {ts[-1]:.2f}) | {B * prompt.shape[1] / ts[len(ts) // 2] * 1e3:10.0f} tokens/s | "
+              f"peak {peak / 2 ** 20:8.1f} MiB ({(peak - held) / 2 ** 20:8.1f} MiB above the {held / 2 ** 20:.1f} MiB "
+              f"held between calls)", flush=True)
+        del gen
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--prefill-chunk", default=None, metavar="N[,N...]",
+                    help="extra lines per batch size: the time and peak memory of one prefill through the "
+                         "training forward and through chunked prefill at each of these chunk sizes")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--ragged", action="store_true", help="extra lines: top-k / top-p and a ragged B = 16 batch")
@@ -108,6 +145,9 @@ def main():
             line += f" | captured {t_g:7.1f} us/step ({B / t_g * 1e6:9.0f} tokens/s)"
         print(line + f" | {sum(calls.values())} launcher calls/step: "
               + ", ".join(f"{k[4:]} x{v}" for k, v in sorted(calls.items())), flush=True)
+        if a.prefill_chunk:
+            del gen, graph, reset
+            prefill_lines(model, P, B, dev, prompt, [int(v) for v in a.prefill_chunk.split(",")])
     if not a.ragged:
         return
     B, T = 16, a.temperature or 0.8
