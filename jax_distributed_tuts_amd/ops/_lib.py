@@ -79,6 +79,10 @@ _SIGS = {
     "jdt_flash_set_head": (None, [c_int]),
     "jdt_flash_set_attn128": (None, [c_int]),
     "jdt_xent_set_rpw": (None, [c_int]),
+    # launch predicates (host only): (logits, logits_f32, ld, C, dlogits, ldd) -> 0 narrow | NV of the wide kernel;
+    # (T, d) -> NV | R << 8 | W << 16 of the LayerNorm backward under the current knobs
+    "jdt_xent_variant": (c_int, [c_void_p, c_int, c_long, c_int, c_void_p, c_long]),
+    "jdt_ln_bwd_variant": (c_int, [c_int, c_int]),
     "jdt_gemm_set_preload": (None, [c_int]),
     "jdt_gemm_set_exact": (None, [c_int]),
     "jdt_gemm_set_dma": (None, [c_int]),

@@ -276,44 +276,54 @@ static int g_ln_rows = 0, g_ln_waves = 0;
 JDT_API void jdt_ln_set_rows(int r) { g_ln_rows = r; }
 JDT_API void jdt_ln_set_waves(int w) { g_ln_waves = w; }
 
+constexpr int ln_bwd_key(int nv, int r, int w) { return nv | r << 8 | w << 16; }
+
+// The ln_bwd_kernel<NV, R, W> instantiation a (T, d) call takes under the current knobs, packed
+// NV | R << 8 | W << 16 (-3: unsupported d).  jdt_ln_bwd launches exactly this; tests assert it.
+// A workgroup = W waves x R rows each.  The column sums cost one same-address
+// atomic per column per workgroup (they serialise in L2), so the rows per
+// workgroup set the atomic count; W spreads those rows over more waves (the
+// per-row work after the loads is serial within a wave).  g_ln_rows /
+// g_ln_waves force R / W (sweeps: tools/bench_ln.py).
+JDT_API int jdt_ln_bwd_variant(int T, int d) {
+  if (d % 8 || d > 2048) return -3;
+  const int nv = (d / 8 + 63) / 64;
+  int R = g_ln_rows, W = g_ln_waves;
+  if (W == 0) W = (nv <= 2 && T >= 1024) ? 16 : 4;
+  if (nv > 2 && W > 4) W = 4;  // LDS image part[W][512 NV]
+  if (R == 0) R = W == 16 ? 2 : (T >= 1024 ? 4 : 2);
+  // register budget: R x NV x 3 row vectors per lane -> R <= 2 at 16 waves, <= 4 at 8
+  if (nv != 1 && nv != 2) return ln_bwd_key(4, R >= 2 ? 2 : 1, 4);
+  if (W >= 16) return ln_bwd_key(nv, R >= 2 ? 2 : 1, 16);
+  if (W >= 8) return ln_bwd_key(nv, R >= 4 ? 4 : (R >= 2 ? 2 : 1), 8);
+  return ln_bwd_key(nv, R >= 8 ? 8 : (R >= 4 ? 4 : (R >= 2 ? 2 : 1)), 4);
+}
+
 // dsum (optional): += colsum(dx), the bias gradient of the layer that produced
 // this LayerNorm's input (a residual-stream Dense), so it needs no pass of its own.
 JDT_API int jdt_ln_bwd(const void* dy, const void* x, const float* mean, const float* rstd, const float* gamma,
                        const void* dres, void* dx, float* dgamma, float* dbeta, float* dsum, int T, int d,
                        void* stream) {
-  if (d % 8 || d > 2048) return -3;
-  const int nv = (d / 8 + 63) / 64;
+  const int variant = jdt_ln_bwd_variant(T, d);
+  if (variant < 0) return variant;
   hipStream_t st = static_cast<hipStream_t>(stream);
   auto a = static_cast<const bf16_t*>(dy);
   auto b = static_cast<const bf16_t*>(x);
   auto r = static_cast<const bf16_t*>(dres);
   auto o = static_cast<bf16_t*>(dx);
   if ((reinterpret_cast<uintptr_t>(gamma) & 15)) return -3;
-  // A workgroup = W waves x R rows each.  The column sums cost one same-address
-  // atomic per column per workgroup (they serialise in L2), so the rows per
-  // workgroup set the atomic count; W spreads those rows over more waves (the
-  // per-row work after the loads is serial within a wave).  g_ln_rows /
-  // g_ln_waves force R / W (sweeps: tools/bench_ln.py).
-  int R = g_ln_rows, W = g_ln_waves;
-  if (W == 0) W = (nv <= 2 && T >= 1024) ? 16 : 4;
-  if (nv > 2 && W > 4) W = 4;  // LDS image part[W][512 NV]
-  if (R == 0) R = W == 16 ? 2 : (T >= 1024 ? 4 : 2);
-#define JDT_LNB(NV_, R_, W_)                                                                                      \
-  hipLaunchKernelGGL((ln_bwd_kernel<NV_, R_, W_>), dim3((T + W_ * R_ - 1) / (W_ * R_)), dim3(64 * W_), 0, st, a, b, \
-                     mean, rstd, gamma, r, o, dgamma, dbeta, dsum, T, d, g_ln_xcd)
-  // register budget: R x NV x 3 row vectors per lane -> R <= 2 at 16 waves, <= 4 at 8
-  switch (nv) {
-    case 1:
-      if (W >= 16) { if (R >= 2) JDT_LNB(1, 2, 16); else JDT_LNB(1, 1, 16); }
-      else if (W >= 8) { if (R >= 4) JDT_LNB(1, 4, 8); else if (R >= 2) JDT_LNB(1, 2, 8); else JDT_LNB(1, 1, 8); }
-      else { if (R >= 8) JDT_LNB(1, 8, 4); else if (R >= 4) JDT_LNB(1, 4, 4); else if (R >= 2) JDT_LNB(1, 2, 4); else JDT_LNB(1, 1, 4); }
-      break;
-    case 2:
-      if (W >= 16) { if (R >= 2) JDT_LNB(2, 2, 16); else JDT_LNB(2, 1, 16); }
-      else if (W >= 8) { if (R >= 4) JDT_LNB(2, 4, 8); else if (R >= 2) JDT_LNB(2, 2, 8); else JDT_LNB(2, 1, 8); }
-      else { if (R >= 8) JDT_LNB(2, 8, 4); else if (R >= 4) JDT_LNB(2, 4, 4); else if (R >= 2) JDT_LNB(2, 2, 4); else JDT_LNB(2, 1, 4); }
-      break;
-    default: if (R >= 2) JDT_LNB(4, 2, 4); else JDT_LNB(4, 1, 4); break;
+#define JDT_LNB(NV_, R_, W_)                                                                                        \
+  case ln_bwd_key(NV_, R_, W_):                                                                                     \
+    hipLaunchKernelGGL((ln_bwd_kernel<NV_, R_, W_>), dim3((T + W_ * R_ - 1) / (W_ * R_)), dim3(64 * W_), 0, st, a, b, \
+                       mean, rstd, gamma, r, o, dgamma, dbeta, dsum, T, d, g_ln_xcd);                               \
+    break
+  switch (variant) {
+    JDT_LNB(1, 2, 16); JDT_LNB(1, 1, 16); JDT_LNB(1, 4, 8); JDT_LNB(1, 2, 8); JDT_LNB(1, 1, 8);
+    JDT_LNB(1, 8, 4); JDT_LNB(1, 4, 4); JDT_LNB(1, 2, 4); JDT_LNB(1, 1, 4);
+    JDT_LNB(2, 2, 16); JDT_LNB(2, 1, 16); JDT_LNB(2, 4, 8); JDT_LNB(2, 2, 8); JDT_LNB(2, 1, 8);
+    JDT_LNB(2, 8, 4); JDT_LNB(2, 4, 4); JDT_LNB(2, 2, 4); JDT_LNB(2, 1, 4);
+    JDT_LNB(4, 2, 4); JDT_LNB(4, 1, 4);
+    default: return -3;
   }
 #undef JDT_LNB
   return HIP_LAUNCH_CHECK();

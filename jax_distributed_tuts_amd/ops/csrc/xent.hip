@@ -58,7 +58,8 @@ __global__ void __launch_bounds__(256) xent_kernel(const void* logits, long ld, 
       const float z = ld_logit<F32>(logits, base + c);
       if (z > best) { best = z; besti = c; }
       const float nm = fmaxf(mx, z);
-      s = s * __expf(mx - nm) + __expf(z - nm);
+      // a lane whose logits so far are all -inf: mx - nm is -inf - -inf (NaN), as in the merge below
+      s = (nm == -INFINITY) ? 0.f : s * __expf(mx - nm) + __expf(z - nm);
       mx = nm;
     }
 #pragma unroll
@@ -224,6 +225,15 @@ using namespace jdt;
 static int g_xent_rpw = 0;
 JDT_API void jdt_xent_set_rpw(int r) { g_xent_rpw = r; }  // sweeps: rows per wave of the wide-vocabulary kernel
 
+// Which kernel a call takes: 0 = xent_kernel (any C, fp32 or bf16 logits, any alignment), else the
+// NV of xent_vec_kernel (1, 2 or 4).  The launcher below calls this; tests assert it per case.
+JDT_API int jdt_xent_variant(const void* logits, int logits_f32, long ld, int C, const void* dlogits, long ldd) {
+  if (!logits_f32 && C >= 256 && C % 8 == 0 && C <= 2048 && ld % 8 == 0 && ldd % 8 == 0 &&
+      (reinterpret_cast<uintptr_t>(logits) & 15) == 0 && (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0)
+    return C <= 512 ? 1 : (C <= 1024 ? 2 : 4);
+  return 0;
+}
+
 // mslab (optional, capacity mslab_cap rows of 4 floats, zero on entry): the wide-vocabulary
 // kernel stores each workgroup's metric sums in its own row instead of adding them to
 // `metrics` (which then is not touched); returns 1 if it did, 0 if `metrics` got them.
@@ -232,8 +242,8 @@ JDT_API int jdt_xent_slab(const void* logits, int logits_f32, long ld, const int
                           float* mslab, int mslab_cap, void* stream) {
   if (M <= 0) return 0;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (!logits_f32 && C >= 256 && C % 8 == 0 && C <= 2048 && ld % 8 == 0 && ldd % 8 == 0 &&
-      (reinterpret_cast<uintptr_t>(logits) & 15) == 0 && (reinterpret_cast<uintptr_t>(dlogits) & 15) == 0) {
+  const int nv = jdt_xent_variant(logits, logits_f32, ld, C, dlogits, ldd);
+  if (nv) {
     // rows per wave: fewer workgroups = fewer same-address metric atomics, which
     // serialise (tools/bench_xent.py, M = 2048: rpw 4 18.8 us, 2 22.1, 1 32.8;
     // M = 512: rpw 2 10.6, 1 11.5)
@@ -244,10 +254,10 @@ JDT_API int jdt_xent_slab(const void* logits, int logits_f32, long ld, const int
                        ? reinterpret_cast<float4*>(mslab) : nullptr;
     auto lg = static_cast<const bf16_t*>(logits);
     auto dl = static_cast<bf16_t*>(dlogits);
-    if (C <= 512)
+    if (nv == 1)
       hipLaunchKernelGGL(xent_vec_kernel<1>, vgrid, dim3(256), 0, st, lg, ld, labels, M, C, rpw, grad_scale, dl, ldd,
                          dbias, metrics, row_loss, slab);
-    else if (C <= 1024)
+    else if (nv == 2)
       hipLaunchKernelGGL(xent_vec_kernel<2>, vgrid, dim3(256), 0, st, lg, ld, labels, M, C, rpw, grad_scale, dl, ldd,
                          dbias, metrics, row_loss, slab);
     else
