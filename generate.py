@@ -8,6 +8,7 @@ one captured decode step replayed per token).
     python generate.py --batch 3 --prompt-lens 5,16,9 --temperature 0.8 --top-k 50 --top-p 0.9 --eos-id 7
     python generate.py --seq-len 1024 --prompt-len 900 --max-new-tokens 100   # a 1024-row KV cache
     python generate.py --seq-len 1024 --prompt-len 900 --prefill-chunk 256    # chunked prefill into the cache
+    python generate.py --beams 4 --length-penalty 1.0 --eos-id 7              # beam search, 4 hypotheses per prompt
 
 Runs the HIP kernels on a GPU and the torch reference paths on CPU tensors when none is
 present.  The prompt is the first ``--prompt-len`` tokens of ``lm_batch``'s sequences;
@@ -16,9 +17,12 @@ present.  The prompt is the first ``--prompt-len`` tokens of ``lm_batch``'s sequ
 printed up to its own final length.  ``--seq-len`` builds the LM with that many learned
 positions (default 128); up to 32768 the decode attention stays on the HIP kernels (split-KV
 past 128 cache rows).  ``--prefill-chunk N`` fills the cache through the append kernels in slices
-of N prompt rows instead of one pass of the training forward.
-Not covered: beam search, repetition penalties, sequences past ``seq_len``, caches longer than
-32768 rows or head dims other than 64 on the HIP path, multi-GPU or pipeline-split generation.
+of N prompt rows instead of one pass of the training forward.  ``--beams W`` (1..8) runs a beam search
+instead of sampling: ``--batch`` prompts with W hypotheses each (a generator of batch * W rows), printed
+best first with their scores, ranked by ``log-probability / length ** --length-penalty``.
+Not covered: beams over ragged prompts, diverse or constrained beam search, repetition penalties,
+sequences past ``seq_len``, caches longer than 32768 rows or head dims other than 64 on the HIP path,
+multi-GPU or pipeline-split generation.
 """
 from __future__ import annotations
 
@@ -53,7 +57,37 @@ def parse_args(argv=None):
     ap.add_argument("--prefill-chunk", type=int, default=None, metavar="N",
                     help="chunked prefill: the prompt goes into the cache in slices of N rows "
                          "(default: one pass of the training forward)")
+    ap.add_argument("--beams", type=int, default=0, metavar="W",
+                    help="beam search with W hypotheses per prompt (1..8) instead of sampling")
+    ap.add_argument("--length-penalty", type=float, default=0.0, metavar="A",
+                    help="beam ranking: log-probability / generated length ** A (0: the raw log-probability)")
     return ap.parse_args(argv)
+
+
+def beam_main(args, tr, prompt, dev):
+    if args.prompt_lens or args.temperature or args.top_k or args.top_p != 1.0:
+        raise SystemExit("--beams is a deterministic search over prompts of one length: it takes none of "
+                         "--prompt-lens, --temperature, --top-k, --top-p")
+    W = args.beams
+    gen = Generator(tr.state.apply_fn, tr.state.params, args.batch * W, dev)
+    sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
+    kw = dict(eos_id=args.eos_id, length_penalty=args.length_penalty, capture=not args.eager,
+              prefill_chunk=args.prefill_chunk)
+    out = gen.beam_search(prompt, args.max_new_tokens, W, **kw)   # first call: allocations and the step capture
+    sync()
+    t0 = time.perf_counter()
+    out = gen.beam_search(prompt, args.max_new_tokens, W, **kw)
+    sync()
+    dt = time.perf_counter() - t0
+    lengths, scores, raw = gen.lengths.cpu().tolist(), gen.beam_scores.cpu().tolist(), gen.beam_logprobs.cpu().tolist()
+    for g, beams in enumerate(out.cpu().tolist()):
+        for r, row in enumerate(beams):
+            print(f"[generate] group {g} beam {r}: score {scores[g][r]:.4f} (log-probability {raw[g][r]:.4f}, "
+                  f"{lengths[g][r] - args.prompt_len} new): {' '.join(str(t) for t in row[:lengths[g][r]])}")
+    print(f"[generate] device={dev} groups={args.batch} beams={W} prompt={args.prompt_len} new={args.max_new_tokens} "
+          f"length_penalty={args.length_penalty} eos_id={args.eos_id} "
+          f"{'eager' if args.eager or dev.type != 'cuda' else 'captured'}: {gen.beam_steps} beam steps, "
+          f"{gen.beam_steps / dt:.1f} steps/s ({dt * 1e3:.2f} ms with the prefill)")
 
 
 def main(args):
@@ -79,6 +113,8 @@ def main(args):
             raise SystemExit(f"--prompt-lens needs one length per sequence ({args.batch}), got {lens.numel()}")
         args.prompt_len = int(lens.max())
     prompt = data.inputs[:args.batch, :args.prompt_len].contiguous().to(dev)
+    if args.beams:
+        return beam_main(args, tr, prompt, dev)
     gen = Generator(tr.state.apply_fn, tr.state.params, args.batch, dev)
     sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
     kw = dict(temperature=args.temperature, seed=args.seed, capture=not args.eager, prompt_lens=lens,

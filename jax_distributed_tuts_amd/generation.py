@@ -39,7 +39,19 @@ the same position.  ``extend(tokens)`` appends to a live cache: a second turn af
 teacher forcing a block of tokens, or scoring a continuation (``logits=True``).  The bits a
 token's attention output gets do not depend on how the tokens were cut into calls or slices.
 
-Out of scope: beam search, repetition penalties, sequences longer than ``seq_len`` (the
+Beam search: ``beam_search(prompt [G, P], n, num_beams=W)`` on a generator of batch G * W keeps W
+hypotheses per prompt; batch row g * W + j is beam slot j of group g, and the position is the shared
+one.  A step is the decode step above followed by two launches of csrc/beam.hip instead of the
+sampler: ``ops.kernels.beam_topw`` (per row: fp32 log-softmax and the W largest logits, or the single
+candidate of a finished beam) and ``ops.kernels.beam_reorder`` (per group the W best of the
+candidates by score, then source slot, then rank; then every layer's cache rows 0..pos and
+``tokens[:, 0..pos]`` of the new slots become their parents', permuted in place, the new tokens go to
+``tokens[:, pos + 1]`` and ``pos`` advances).  The beam state (``BeamState``) lives on the device and
+both launches read ``pos`` there, so the captured beam step replays for every token too.
+
+Out of scope: beams over ragged prompts (per-row positions), diverse or constrained beam search, a
+beam cache that re-routes through an indirection table instead of copying, sharing the prompt's
+cache rows between the beams of a group, repetition penalties, sequences longer than ``seq_len`` (the
 learned positions end there), multi-GPU or pipeline-split generation, paged or compacted
 caches, ``generate()`` continuing a live cache, a split-KV append kernel (an append workgroup
 walks the whole cache above its query tile), removing finished rows from the batch, and head
@@ -84,10 +96,41 @@ class KVCache:
         if cfg.seq_len > K.AD_CHUNK_ROWS:
             chunks = (cfg.seq_len + K.AD_CHUNK_ROWS - 1) // K.AD_CHUNK_ROWS
             self.split_ws = torch.zeros(batch * H, chunks, K.AD_SLOT_FLOATS, dtype=torch.float32, device=device)
+        self._history_ptrs = None
 
     @property
     def live_pos(self) -> torch.Tensor:
         return self.pos_rows if self.per_row else self.pos
+
+    def history_ptrs(self):
+        """``ops.kernels.cache_ptr_table`` of every layer's K, then V: the table the beam reorder's one
+        launch walks.  Built on first use and kept (the cache tensors are never reallocated)."""
+        if self._history_ptrs is None:
+            self._history_ptrs = K.cache_ptr_table(self.k + self.v)
+        return self._history_ptrs
+
+
+class BeamState:
+    """The device state of a beam search over ``batch`` = G * W rows: per slot ``score`` (fp32, the sum
+    of the chosen tokens' log-probabilities), ``done`` and ``length`` (int32, generated tokens), the
+    last step's ``parent`` (the slot 0..W-1 of the same group whose history the slot continues) and
+    ``token``, and the stage-1 candidate scratch ``cand`` = (token int32 [B, 8], score fp32 [B, 8])."""
+
+    def __init__(self, batch: int, W: int, device):
+        self.W, self.G, self.eos_id = W, batch // W, -1
+        i32 = lambda: torch.zeros(batch, dtype=torch.int32, device=device)  # noqa: E731
+        self.score = torch.zeros(batch, dtype=torch.float32, device=device)
+        self.done, self.length, self.parent, self.token = i32(), i32(), i32(), i32()
+        self.cand = (torch.full((batch, K.BEAM_MAX_W), -1, dtype=torch.int32, device=device),
+                     torch.full((batch, K.BEAM_MAX_W), float("-inf"), dtype=torch.float32, device=device))
+
+    def reset(self, eos_id: int):
+        """Slot 0 of each group at score 0, the others at -inf: the first step fans out from one beam."""
+        self.eos_id = eos_id
+        self.score.fill_(float("-inf"))
+        self.score.view(self.G, self.W)[:, 0] = 0.0
+        for t in (self.done, self.length, self.parent, self.token):
+            t.zero_()
 
 
 class Generator:
@@ -110,8 +153,13 @@ class Generator:
         self._chunk_bufs: dict = {}                  # chunk size -> advance's embedded rows [B * chunk, d_model]
         self._live = False                           # a prefill has run: extend may append
         # (temperature, seed) -> (graph, its logits); any other sampler setting or the
-        # per-row mode: (temperature, seed, top_k, top_p, eos_id, per_row)
+        # per-row mode: (temperature, seed, top_k, top_p, eos_id, per_row); the beam step: ("beam", W, eos_id)
         self._graphs: dict = {}
+        self.beam: Optional[BeamState] = None        # the live beam search's state (beam_begin)
+        self._beam_states: dict = {}                 # W -> BeamState (kept: a captured step holds its pointers)
+        self.beam_scores: Optional[torch.Tensor] = None    # fp32 [G, W]: the last beam_search's ranking scores
+        self.beam_logprobs: Optional[torch.Tensor] = None  # fp32 [G, W]: its raw log-probability sums
+        self.beam_steps = 0                          # steps the last beam_search ran
 
     # ------------------------------------------------------------------ prefill
     def prefill(self, prompt: torch.Tensor, prompt_lens: Optional[torch.Tensor] = None, *,
@@ -307,22 +355,24 @@ class Generator:
             key += (self.top_k, self.top_p, self.eos_id, self.kv.per_row)
         return key
 
-    def _replay(self):
+    def _replay(self, step=None, key=None):
         """The sampling step as a graph replay (captured on first use per sampler setting;
         one stream, no parallel branches).  The eager step before the capture is a real
-        step: it also creates every lazily allocated workspace outside the capture."""
-        key = self._graph_key()
+        step: it also creates every lazily allocated workspace outside the capture.
+        ``step`` / ``key``: another step function and its graph key (the beam step)."""
+        step = self.step if step is None else step
+        key = self._graph_key() if key is None else key
         ent = self._graphs.get(key)
         if ent is None:
-            eager = self.step()
+            eager = step()
             torch.cuda.synchronize(self.device)
-            g = capture_graph(self.step)   # records only: nothing runs, pos and the cache stay
+            g = capture_graph(step)   # records only: nothing runs, pos and the cache stay
             self._graphs[key] = (g, self.logits)
             self.logits = eager
             return
         g, logits = ent
         if g is None:   # the capture was refused: stay eager
-            self.step()
+            step()
             return
         g.replay()
         self.logits = logits
@@ -384,4 +434,88 @@ class Generator:
         self.lengths = kv.pos_rows + 1
         out = kv.tokens[:, :longest + max_new_tokens].clone()
         out[torch.arange(out.shape[1], device=self.device)[None] >= self.lengths[:, None]] = pad_id
+        return out
+
+    # ------------------------------------------------------------------ beam search
+    def beam_begin(self, prompt: torch.Tensor, num_beams: int, eos_id: Optional[int] = None,
+                   prefill_chunk: Optional[int] = None) -> BeamState:
+        """Start a beam search: ``prompt`` int [G, P] with G * num_beams == batch is repeated over each
+        group's slots and prefilled (shared position, pos = P - 1), and the beam state is reset.
+        Returns the ``BeamState`` (also ``self.beam``); ``beam_step`` runs the steps."""
+        c, W = self.model.cfg, int(num_beams)
+        if not 1 <= W <= K.BEAM_MAX_W:
+            raise ValueError(f"num_beams must be in 1..{K.BEAM_MAX_W}, got {num_beams}")
+        if self.batch % W:
+            raise ValueError(f"num_beams {W} does not divide the generator's batch {self.batch}")
+        if prompt.dim() != 2 or prompt.shape[0] * W != self.batch:
+            raise ValueError(f"prompt must be [{self.batch // W}, P] for {W} beams on a batch of {self.batch}, "
+                             f"got {tuple(prompt.shape)}")
+        if W > c.vocab_size:
+            raise ValueError(f"num_beams {W} exceeds the vocabulary {c.vocab_size}")
+        eos = -1 if eos_id is None else int(eos_id)
+        if eos >= c.vocab_size or (eos_id is not None and eos < 0):
+            raise ValueError(f"eos_id {eos_id} outside [0, {c.vocab_size})")
+        self.prefill(prompt.repeat_interleave(W, dim=0), chunk=prefill_chunk)
+        st = self._beam_states.get(W)
+        if st is None:
+            st = self._beam_states[W] = BeamState(self.batch, W, self.device)
+        st.reset(eos)
+        self.beam = st
+        return st
+
+    def beam_step(self) -> torch.Tensor:
+        """One beam step at position ``pos``: the decode step, then ``beam_topw`` and ``beam_reorder``
+        (which writes ``tokens[:, pos + 1]`` and advances ``pos``).  Returns the step's logits
+        [B, vocab]; ``self.beam.parent`` / ``.token`` hold the step's choice."""
+        kv, P, st = self.kv, self.P, self.beam
+        if st is None or kv.per_row:
+            raise ValueError("beam_step needs a beam search in progress: call beam_begin first")
+        K.embed_decode(kv.tokens, P.s("embed/wte"), P.s("embed/wpe"), kv.pos, out=self.x)
+        self.logits = self.model.decode_step(P, kv, self.x)
+        K.beam_topw(self.logits, st.score, st.done, kv.pos, st.W, st.eos_id, seq_len=self.model.cfg.seq_len,
+                    out=st.cand)
+        K.beam_reorder(st.cand, kv.k, kv.v, kv.tokens, st.score, st.done, st.length, st.parent, st.token, kv.pos,
+                       st.W, st.eos_id, ptrs=kv.history_ptrs() if self.device.type == "cuda" else None)
+        return self.logits
+
+    def beam_search(self, prompt: torch.Tensor, max_new_tokens: int, num_beams: int = 1, *,
+                    eos_id: Optional[int] = None, length_penalty: float = 0.0, pad_id: int = 0,
+                    capture: bool = True, prefill_chunk: Optional[int] = None) -> torch.Tensor:
+        """``prompt`` int [G, P] -> int32 [G, num_beams, P + max_new_tokens]: per prompt the
+        ``num_beams`` hypotheses the search ends with, best first.  The generator's batch must be
+        G * num_beams.  A hypothesis that emits ``eos_id`` is finished (the EOS is its last token, its
+        score stops changing) and keeps competing; the loop ends early once every slot is finished
+        (checked every 16 steps).  Ranking: ``score / max(length, 1) ** length_penalty`` with ``length``
+        the generated tokens (0.0: the raw sum of log-probabilities), stable.  ``pad_id`` fills
+        positions at and past each hypothesis' final length.  Sets ``beam_scores`` (the ranking
+        scores) and ``beam_logprobs`` (the raw sums), fp32 [G, W], and ``lengths`` (int32 [G, W],
+        prompt included).  ``capture`` (GPU only): the beam step is captured once per
+        (num_beams, eos_id) and replayed per token."""
+        c = self.model.cfg
+        Pn = prompt.shape[1] if prompt.dim() == 2 else 0
+        if max_new_tokens < 0 or Pn + max_new_tokens > c.seq_len:
+            raise ValueError(f"prompt length {Pn} + max_new_tokens {max_new_tokens} exceeds seq_len "
+                             f"{c.seq_len} (the learned positions end there)")
+        st = self.beam_begin(prompt, num_beams, eos_id=eos_id, prefill_chunk=prefill_chunk)
+        G, W = st.G, st.W
+        graph = capture and self.device.type == "cuda"
+        key = ("beam", W, st.eos_id)
+        self.beam_steps = 0
+        for i in range(1, max_new_tokens + 1):
+            if graph:
+                self._replay(self.beam_step, key)
+            else:
+                self.beam_step()
+            self.beam_steps = i
+            # a host read serialises the replay loop: look only every 16 steps
+            if st.eos_id >= 0 and i % 16 == 0 and i < max_new_tokens and bool(st.done.all()):
+                break
+        raw, length = st.score.view(G, W), st.length.view(G, W)
+        rank = raw / length.clamp(min=1).to(torch.float32) ** float(length_penalty)
+        order = torch.sort(rank, dim=1, descending=True, stable=True).indices
+        self.beam_scores, self.beam_logprobs = rank.gather(1, order), raw.gather(1, order)
+        self.lengths = (Pn + length).gather(1, order).to(torch.int32)
+        out = self.kv.tokens[:, :Pn + max_new_tokens].view(G, W, -1)
+        out = out.gather(1, order[:, :, None].expand(-1, -1, out.shape[2]))   # a copy, best first
+        out[torch.arange(out.shape[2], device=self.device)[None, None] >= self.lengths[:, :, None]] = pad_id
         return out

@@ -151,6 +151,14 @@ _SIGS = {
     # (logits, ld, B, V, temperature, seed, stream_id, tokens, S_max, pos, end, eos_id, top_k, top_p, stream)
     "jdt_sample_rows": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_ulonglong, ctypes.c_uint, c_void_p, c_int,
                                 c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
+    # csrc/beam.hip: (logits, ld, B, V, W, score, done, eos_id, cand_tok, cand_score, pos, S_max, stream)
+    "jdt_beam_topw": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                              c_void_p, c_int, c_void_p]),
+    # (cand_tok, cand_score, caches_dev, caches_host, n_caches, tokens, score, done, length, parent, token, pos,
+    #  ticket, B, W, H, Dh, S_max, eos_id, stream)
+    "jdt_beam_reorder": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                 c_int, c_void_p]),
 }
 
 

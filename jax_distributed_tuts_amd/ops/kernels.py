@@ -1353,3 +1353,128 @@ def sample_tokens(logits: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor,
         rc = L.jdt_sample_filtered(*head, _ptr(ticket), int(top_k), float(top_p), _lib.stream_ptr())
         _lib.check(rc, "jdt_sample_filtered")
     return tokens
+
+
+# ----------------------------------------------------------------------------- beam search (csrc/beam.hip)
+BEAM_MAX_W = 8   # beams per group == entries per row of the candidate scratch (csrc/beam.hip BM_MAXW)
+
+
+def cache_ptr_table(tensors):
+    """The base pointers of ``tensors`` as (device int64 tensor, host ctypes array): the table
+    ``beam_reorder`` hands to its single launch.  The host copy serves the launcher's checks."""
+    addrs = [int(t.data_ptr()) for t in tensors]
+    dev = torch.tensor(addrs, dtype=torch.int64, device=tensors[0].device)
+    return dev, (ctypes.c_void_p * len(addrs))(*addrs)
+
+
+def beam_merge(cand_tok: torch.Tensor, cand_score: torch.Tensor, W: int):
+    """Stage 2 of a beam step on any device, in torch: per group of W rows the W best of the rows'
+    candidates (``cand_tok`` int32 [B, 8], -1: empty; ``cand_score`` fp32 [B, 8]) by score
+    descending, then source slot, then stage-1 rank.  Returns (parent, token, score), each [B]:
+    new slot j of a group continues slot ``parent[j]`` (0..W-1) of the same group."""
+    B = cand_tok.shape[0]
+    G = B // W
+    tok = cand_tok[:, :W].reshape(G, W * W).long()
+    sc = cand_score[:, :W].reshape(G, W * W)
+    o1 = torch.sort(sc, dim=1, descending=True, stable=True).indices          # ties keep (slot, rank) order
+    o2 = torch.sort((tok.gather(1, o1) < 0).to(torch.uint8), dim=1, stable=True).indices   # empty ones last
+    best = o1.gather(1, o2)[:, :W]
+    return ((best // W).reshape(B).to(torch.int32), tok.gather(1, best).reshape(B).to(torch.int32),
+            sc.gather(1, best).reshape(B))
+
+
+def beam_topw(logits: torch.Tensor, score: torch.Tensor, done: torch.Tensor, pos: torch.Tensor, W: int,
+              eos_id: int = -1, *, seq_len: int, out=None):
+    """Stage 1 of a beam step.  ``logits`` [B, V] bf16, ``score`` fp32 [B], ``done`` int32 [B]; row
+    g * W + j is beam slot j of group g.  Per row, in fp32: gmx = max x, lse = log(sum exp(x - gmx)),
+    and for the row's W largest logits (exact on the bf16 values, ties to the lower token index, in
+    that order) the candidates (token, score[w] + ((x - gmx) - lse)).  A done row has the single
+    candidate (eos_id, score[w]).  ``out`` = (cand_tok int32 [B, 8], cand_score fp32 [B, 8]); unused
+    entries get token -1 and score -inf.  ``pos + 1 >= seq_len``: nothing is written."""
+    B, V = logits.shape
+    if not 1 <= W <= BEAM_MAX_W or B % W or W > V or eos_id >= V:
+        raise ValueError(f"beam_topw: W={W} must be in 1..{BEAM_MAX_W}, divide B={B} and be <= V={V}; eos_id={eos_id}")
+    if out is None:
+        out = (torch.full((B, BEAM_MAX_W), -1, dtype=torch.int32, device=logits.device),
+               torch.full((B, BEAM_MAX_W), float("-inf"), dtype=torch.float32, device=logits.device))
+    ct, cs = out
+    assert ct.dtype == torch.int32 and cs.dtype == torch.float32 and ct.shape == cs.shape == (B, BEAM_MAX_W)
+    assert score.dtype == torch.float32 and done.dtype == torch.int32 and score.numel() == done.numel() == B
+    if not _is_gpu(logits):
+        p = int(pos[0])
+        if p < 0 or p + 1 >= seq_len:
+            return out
+        x = _bf(logits.float())
+        gmx = x.max(-1, keepdim=True).values
+        lp = (x - gmx) - torch.log(torch.exp(x - gmx).sum(-1, keepdim=True))
+        xs, order = torch.sort(x, dim=-1, descending=True, stable=True)   # stable: ties to the lower index
+        top = order[:, :W]
+        ct.fill_(-1)
+        cs.fill_(float("-inf"))
+        ct[:, :W] = top.to(torch.int32)
+        cs[:, :W] = score[:, None] + lp.gather(1, top)
+        fin = done != 0
+        ct[fin] = -1
+        cs[fin] = float("-inf")
+        ct[fin, 0] = eos_id
+        cs[fin, 0] = score[fin]
+        return out
+    assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1 and ct.is_contiguous() and cs.is_contiguous()
+    rc = _lib.lib().jdt_beam_topw(_ptr(logits), logits.stride(0), B, V, int(W), _ptr(score), _ptr(done), int(eos_id),
+                                  _ptr(ct), _ptr(cs), _ptr(pos), int(seq_len), _lib.stream_ptr())
+    _lib.check(rc, "jdt_beam_topw")
+    return out
+
+
+def beam_reorder(cand, k_list, v_list, tokens: torch.Tensor, score: torch.Tensor, done: torch.Tensor,
+                 length: torch.Tensor, parent: torch.Tensor, token: torch.Tensor, pos: torch.Tensor, W: int,
+                 eos_id: int = -1, ptrs=None):
+    """Stage 2 of a beam step and the re-routing of the histories, in place.  ``cand``: ``beam_topw``'s
+    (cand_tok, cand_score).  With (parent, token, score) = ``beam_merge(cand)``, new slot j of group g
+    gets rows 0..pos of every tensor of ``k_list`` / ``v_list`` ([B, H, S_max, Dh] bf16) and
+    ``tokens[:, 0..pos]`` (int32 [B, S_max]) of row g * W + parent[j]; then ``tokens[g * W + j, pos + 1] =
+    token[j]``, ``done`` = parent's done or token == eos_id, ``length`` = parent's length + (0 if the
+    parent was done else 1), ``parent`` / ``token`` keep this step's choice, and ``pos += 1``.
+    ``pos + 1 >= S_max``: nothing changes.  ``ptrs``: ``cache_ptr_table(k_list + v_list)``, built once by
+    the caller (``KVCache.history_ptrs``); ``None``: built here."""
+    ct, cs = cand
+    B, S_max = tokens.shape
+    caches = list(k_list) + list(v_list)
+    if not 1 <= W <= BEAM_MAX_W or B % W:
+        raise ValueError(f"beam_reorder: W={W} must be in 1..{BEAM_MAX_W} and divide B={B}")
+    assert tokens.dtype == torch.int32 and pos.numel() == 1
+    for t in (done, length, parent, token):
+        assert t.dtype == torch.int32 and t.numel() == B
+    if not _is_gpu(tokens):
+        p = int(pos[0])
+        if p < 0 or p + 1 >= S_max:
+            return
+        par, tok, sc = beam_merge(ct, cs, W)
+        src = (torch.arange(B) // W * W + par).long()
+        for c in caches:
+            c[:, :, :p + 1] = c.index_select(0, src)[:, :, :p + 1]
+        tokens[:, :p + 1] = tokens.index_select(0, src)[:, :p + 1]
+        tokens[:, p + 1] = tok
+        pd, pl = done.index_select(0, src), length.index_select(0, src)
+        score.copy_(sc)
+        done.copy_(((pd != 0) | ((tok == eos_id) & (eos_id >= 0))).to(torch.int32))
+        length.copy_(pl + (pd == 0).to(torch.int32))
+        parent.copy_(par)
+        token.copy_(tok)
+        pos.add_(1)
+        return
+    H, Dh = (caches[0].shape[1], caches[0].shape[3]) if caches else (1, AD_HEAD_DIM)
+    for c in caches:
+        assert c.dtype == torch.bfloat16 and c.is_contiguous() and c.shape == (B, H, S_max, Dh)
+    assert tokens.is_contiguous() and ct.is_contiguous() and cs.is_contiguous()
+    if ptrs is None and caches:
+        ptrs = cache_ptr_table(caches)
+    dev_tab, host_tab = ptrs if caches else (None, None)
+    key = str(tokens.device)
+    ticket = _SAMPLE_TICKET.get(key)
+    if ticket is None:   # the kernel leaves it zero again: one word serves every call on the device
+        ticket = _SAMPLE_TICKET[key] = torch.zeros(1, dtype=torch.int32, device=tokens.device)
+    rc = _lib.lib().jdt_beam_reorder(_ptr(ct), _ptr(cs), _ptr(dev_tab), host_tab, len(caches), _ptr(tokens),
+                                     _ptr(score), _ptr(done), _ptr(length), _ptr(parent), _ptr(token), _ptr(pos),
+                                     _ptr(ticket), B, int(W), int(H), int(Dh), S_max, int(eos_id), _lib.stream_ptr())
+    _lib.check(rc, "jdt_beam_reorder")

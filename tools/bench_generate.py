@@ -3,7 +3,7 @@ default TransformerConfig at B = 1 and B = 16: us per decode step and tokens/s, 
 eagerly against one captured step replayed per token, plus the kernel-launcher calls per step.
 
     python tools/bench_generate.py [--steps 100] [--temperature 0.0] [--ragged] [--seq-len N] [--prompt-len P]
-                                   [--prefill-chunk N[,N...]]
+                                   [--prefill-chunk N[,N...]] [--beams W[,W...]]
 
 Each figure: ``--steps`` decode steps after a 16-token prefill, timed with events around the
 whole loop (prefill excluded), median of 5 runs.  ``--seq-len N`` > 128 builds the LM with an
@@ -14,7 +14,9 @@ temperature (``--temperature``, or 0.8 when that is 0): the uniform batch with t
 top-p sampler (k = 50, p = 0.9), and a ragged batch (prompt lengths 1..16, per-row positions)
 with the plain and with the filtered sampler.  ``--prefill-chunk 64,256,1024`` adds, per batch
 size, the time and the peak memory of one prefill of the same prompt through the training forward
-and through chunked prefill at each chunk size (``prefill_lines``).
+and through chunked prefill at each chunk size (``prefill_lines``).  ``--beams 4,8`` adds, per batch
+size G (then the number of prompts) and beam count W, the beam step of ``Generator.beam_search`` on G x W
+rows beside the plain sampled step at the same batch and depth (``beam_lines``).
 """
 import argparse
 import os
@@ -27,6 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from jax_distributed_tuts_amd.generation import Generator  # noqa: E402
 from jax_distributed_tuts_amd.models.transformer import TransformerConfig, TransformerLM  # noqa: E402
 from jax_distributed_tuts_amd.ops import _lib  # noqa: E402
+from jax_distributed_tuts_amd.ops import kernels as K  # noqa: E402
 from jax_distributed_tuts_amd.utils.flat import FlatParams  # noqa: E402
 
 PROMPT = 16
@@ -50,12 +53,12 @@ class _CountingLib:
         return counted
 
 
-def launches_per_step(gen):
+def launches_per_step(gen, step=None):
     real = _lib.lib
     proxy = _CountingLib(real())
     _lib.lib = lambda: proxy
     try:
-        gen.step()
+        (step or gen.step)()
     finally:
         _lib.lib = real
     return proxy.calls
@@ -105,8 +108,65 @@ def prefill_lines(model, P, B, dev, prompt, chunks, reps=5):
         del gen
 
 
+def beam_lines(model, P, G, dev, beams, steps, temperature, depth):
+    """Per beam count W, on a generator of G x W rows: us per beam step (decode step + ``beam_topw`` +
+    ``beam_reorder``), eager and captured, with its launcher calls; the select + reorder launches alone
+    (the step's own candidates and position, eager, so launch-bound at small caches); the share of
+    slots that changed parent per step (what the reorder has to move); and the plain sampled step of
+    the same generator at the same batch and depth."""
+    cfg = model.cfg
+    for W in beams:
+        B = G * W
+        gen = Generator(model, P, B, dev)
+        prompt = torch.randint(0, cfg.vocab_size, (G, PROMPT), generator=torch.Generator().manual_seed(1))
+        prompt = prompt.to(torch.int32).to(dev)
+        gen.beam_search(prompt, 2, W, capture=True)   # warm-up + the step capture
+        graph = gen._graphs[("beam", W, -1)][0]
+        reset = lambda: gen.beam_begin(prompt, W)  # noqa: E731
+        reset()
+        calls = launches_per_step(gen, gen.beam_step)
+        t_e = timed(gen.beam_step, reset, steps)
+        st, kv = gen.beam, gen.kv
+        reset()
+        moved = torch.zeros((), dtype=torch.int64, device=dev)
+        own = torch.arange(B, device=dev) % W
+        for _ in range(steps):
+            gen.beam_step()
+            moved += (st.parent != own).sum()
+
+        def tail():
+            K.beam_topw(gen.logits, st.score, st.done, kv.pos, W, -1, seq_len=cfg.seq_len, out=st.cand)
+            K.beam_reorder(st.cand, kv.k, kv.v, kv.tokens, st.score, st.done, st.length, st.parent, st.token, kv.pos,
+                           W, -1, ptrs=kv.history_ptrs())
+
+        def reset_tail():
+            reset()
+            gen.beam_step()   # logits and a spread-out beam state to select from
+
+        t_t = timed(tail, reset_tail, steps - 1)
+        line = (f"beam     G={G:2d} W={W} B={B:3d}{depth}: eager {t_e:7.1f} us/step")
+        if graph is not None:
+            line += f" | captured {timed(graph.replay, reset, steps):7.1f} us/step"
+        line += (f" | select + reorder alone, eager {t_t:6.1f} us | {float(moved) / (steps * B):.2f} of the slots "
+                 f"change parent per step | {sum(calls.values())} launcher calls/step: "
+                 + ", ".join(f"{k[4:]} x{v}" for k, v in sorted(calls.items())))
+        print(line, flush=True)
+        wide = prompt.repeat_interleave(W, 0)
+        gen.generate(wide, 2, temperature=temperature, capture=True)
+        pgraph = gen._graphs[(float(temperature), 0)][0]
+        preset = lambda: gen.prefill(wide)  # noqa: E731
+        line = f"  plain step B={B:3d} T={temperature}{depth}: eager {timed(gen.step, preset, steps):7.1f} us/step"
+        if pgraph is not None:
+            line += f" | captured {timed(pgraph.replay, preset, steps):7.1f} us/step"
+        print(line, flush=True)
+        del gen, graph, pgraph, reset, preset
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--beams", default=None, metavar="W[,W...]",
+                    help="extra lines per batch size G: the beam step on G x W rows, eager and captured, beside "
+                         "the plain sampled step at the same batch")
     ap.add_argument("--prefill-chunk", default=None, metavar="N[,N...]",
                     help="extra lines per batch size: the time and peak memory of one prefill through the "
                          "training forward and through chunked prefill at each of these chunk sizes")
@@ -148,6 +208,8 @@ def main():
         if a.prefill_chunk:
             del gen, graph, reset
             prefill_lines(model, P, B, dev, prompt, [int(v) for v in a.prefill_chunk.split(",")])
+        if a.beams:
+            beam_lines(model, P, B, dev, [int(v) for v in a.beams.split(",")], a.steps, a.temperature, depth)
     if not a.ragged:
         return
     B, T = 16, a.temperature or 0.8
