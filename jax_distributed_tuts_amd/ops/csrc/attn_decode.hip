@@ -27,6 +27,7 @@
 // sample:       argmax (temperature 0) or inverse-CDF sampling of softmax(logits / T),
 //               optionally restricted to the top-k / top-p set (FILT = true)
 #include "common.h"
+#include "row_select.h"
 
 #include <limits.h>
 
@@ -40,14 +41,6 @@ constexpr int AD_CHUNK = AD_KPP * AD_NP;   // keys per workgroup of the split-KV
 constexpr int AD_LONG_SMAX = 32768;        // cache rows per head the split-KV launchers cover
 constexpr int AD_SLOT = 2 + AD_DH;         // fp32 words of a partial: max, sum, unnormalised o[64]
 constexpr int AD_CB = 8;                   // partials the combine loads at a time
-
-__device__ __forceinline__ void unpack8(const u32x4& r, float (&x)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    x[2 * j] = bf2f((bf16_t)(r[j] & 0xffff));
-    x[2 * j + 1] = bf2f((bf16_t)(r[j] >> 16));
-  }
-}
 
 // sum over the 8 lanes of an aligned lane octet (all lanes active): the first three
 // steps of wave_sum_dpp; every lane of the octet gets the same value
@@ -264,48 +257,11 @@ __global__ void __launch_bounds__(256) embed_append_kernel(const int* __restrict
   *reinterpret_cast<u32x4*>(out + (long)row * d + c) = bf16x8_add(a, e);
 }
 
-// 8 logits from column i0 (a multiple of 8) of a row; columns >= V read as -inf
-__device__ __forceinline__ void logits8(const bf16_t* row, int i0, int V, bool vec, float (&x)[8]) {
-  if (vec) {   // V % 8 == 0 and a 16-byte aligned row: i0 < V covers all 8
-    unpack8(*reinterpret_cast<const u32x4*>(row + i0), x);
-    return;
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) x[e] = i0 + e < V ? bf2f(row[i0 + e]) : -INFINITY;
-}
-
-// Order-preserving 16-bit key of a bf16 value held in a float: a larger value has a larger
-// key.  -0 shares the key of +0 and a NaN gets key 0 (below -inf), so it is never kept.
-__device__ __forceinline__ unsigned key16(float x) {
-  unsigned h = __float_as_uint(x) >> 16;
-  if ((h & 0x7fffu) > 0x7f80u) return 0u;
-  if (h == 0x8000u) h = 0u;
-  return (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u);
-}
-
 // the sampling weight of a logit; FILT: 0 below the threshold key
 template <bool FILT>
 __device__ __forceinline__ float weight(float x, float gmx, float inv_t, unsigned thr) {
   if (FILT && key16(x) < thr) return 0.f;
   return __expf((x - gmx) * inv_t);
-}
-
-// inclusive prefix sum of v over the workgroup's 256 threads (every thread calls it)
-__device__ __forceinline__ int block_scan_incl(int v, int* s_tmp) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int t = __shfl_up(v, o, WAVE);
-    if (lane >= o) v += t;
-  }
-  __syncthreads();   // the previous call's readers are done with s_tmp
-  if (lane == WAVE - 1) s_tmp[w] = v;
-  __syncthreads();
-  int off = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-    if (k < w) off += s_tmp[k];
-  return v + off;
 }
 
 // The threshold key max(key_k, key_p) of a row (every thread of the workgroup calls it and
@@ -506,9 +462,6 @@ __global__ void __launch_bounds__(256) sample_kernel(const bf16_t* __restrict__ 
 
 }  // namespace jdt
 using namespace jdt;
-
-
-static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
 
 template <bool ROWS>
 static int attn_decode_launch(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H,

@@ -29,8 +29,9 @@
 // The last workgroup to take an arrival ticket stores pos + 1 and re-arms the ticket (the
 // sampler's scheme, csrc/attn_decode.hip: every workgroup has read pos by then).
 //
-// logits8 / key16 / the block scan mirror the sampler's helpers of the same purpose.
+// logits8 / key16 / block_scan_incl are the sampler's too: csrc/row_select.h.
 #include "common.h"
+#include "row_select.h"
 
 #include <limits.h>
 
@@ -41,47 +42,6 @@ constexpr int BM_DH = 64;        // head dim: a cache row is 8 pieces of 16 byte
 constexpr int BM_ROWS = 128;     // cache rows (token columns) per workgroup of the reorder
 constexpr int BM_PASS = 32;      // rows per pass: 256 threads / 8 pieces per row
 constexpr int BM_SMAX = 32768;   // cache rows per head the decode kernels cover
-
-__device__ __forceinline__ void bm_logits8(const bf16_t* row, int i0, int V, bool vec, float (&x)[8]) {
-  if (vec) {   // V % 8 == 0 and a 16-byte aligned row: i0 < V covers all 8
-    const u32x4 r = *reinterpret_cast<const u32x4*>(row + i0);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      x[2 * j] = bf2f((bf16_t)(r[j] & 0xffff));
-      x[2 * j + 1] = bf2f((bf16_t)(r[j] >> 16));
-    }
-    return;
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) x[e] = i0 + e < V ? bf2f(row[i0 + e]) : -INFINITY;
-}
-
-// Order-preserving 16-bit key of a bf16 value held in a float: a larger value has a larger key.
-// -0 shares the key of +0 and a NaN gets key 0 (below -inf).
-__device__ __forceinline__ unsigned bm_key16(float x) {
-  unsigned h = __float_as_uint(x) >> 16;
-  if ((h & 0x7fffu) > 0x7f80u) return 0u;
-  if (h == 0x8000u) h = 0u;
-  return (h & 0x8000u) ? (~h & 0xffffu) : (h | 0x8000u);
-}
-
-// inclusive prefix sum of v over the workgroup's 256 threads (every thread calls it)
-__device__ __forceinline__ int bm_scan_incl(int v, int* s_tmp) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < WAVE; o <<= 1) {
-    const int t = __shfl_up(v, o, WAVE);
-    if (lane >= o) v += t;
-  }
-  __syncthreads();   // the previous call's readers are done with s_tmp
-  if (lane == WAVE - 1) s_tmp[w] = v;
-  __syncthreads();
-  int off = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-    if (k < w) off += s_tmp[k];
-  return v + off;
-}
 
 // One workgroup per batch row; thread t owns the contiguous columns [t * per, (t + 1) * per) (the
 // sampler's chunking).  gmx = max x; lse = logf(sum expf(x - gmx)) with libm's expf / logf (not the
@@ -118,7 +78,7 @@ __global__ void __launch_bounds__(256) beam_topw_kernel(const bf16_t* __restrict
   float mx = -INFINITY;
   for (int i0 = beg; i0 < end; i0 += 8) {
     float x[8];
-    bm_logits8(row, i0, V, vec, x);
+    logits8(row, i0, V, vec, x);
 #pragma unroll
     for (int e = 0; e < 8; ++e) mx = fmaxf(mx, x[e]);
   }
@@ -131,7 +91,7 @@ __global__ void __launch_bounds__(256) beam_topw_kernel(const bf16_t* __restrict
   float ts = 0.f;
   for (int i0 = beg; i0 < end; i0 += 8) {
     float x[8];
-    bm_logits8(row, i0, V, vec, x);
+    logits8(row, i0, V, vec, x);
 #pragma unroll
     for (int e = 0; e < 8; ++e) ts += expf(x[e] - gmx);   // a column past V is -inf: adds an exact 0
   }
@@ -148,17 +108,17 @@ __global__ void __launch_bounds__(256) beam_topw_kernel(const bf16_t* __restrict
     __syncthreads();
     for (int i0 = beg; i0 < end; i0 += 8) {
       float x[8];
-      bm_logits8(row, i0, V, vec, x);
+      logits8(row, i0, V, vec, x);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const unsigned key = bm_key16(x[e]);
+        const unsigned key = key16(x[e]);
         if (i0 + e < V && (level == 0 || (key >> 8) == hi_bin))
           atomicAdd(&s_hist[level == 0 ? key >> 8 : key & 255u], 1);   // integer counts: order-free
       }
     }
     __syncthreads();
     const int bin = 255 - tid, h = s_hist[bin];   // descending: thread 0 has the top bin
-    const int inc = bm_scan_incl(h, s_scan);
+    const int inc = block_scan_incl(h, s_scan);
     if (inc >= want && inc - h < want) {   // exactly one thread: the counts sum to V >= W
       s_sel[0] = bin;
       s_sel[1] = want - (inc - h);
@@ -173,18 +133,18 @@ __global__ void __launch_bounds__(256) beam_topw_kernel(const bf16_t* __restrict
   int neq = 0;
   for (int i0 = beg; i0 < end; i0 += 8) {
     float x[8];
-    bm_logits8(row, i0, V, vec, x);
+    logits8(row, i0, V, vec, x);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) neq += (i0 + e < V && bm_key16(x[e]) == key_w) ? 1 : 0;
+    for (int e = 0; e < 8; ++e) neq += (i0 + e < V && key16(x[e]) == key_w) ? 1 : 0;
   }
-  int eq_rank = bm_scan_incl(neq, s_scan) - neq;   // columns at key_w left of this thread's chunk
+  int eq_rank = block_scan_incl(neq, s_scan) - neq;   // columns at key_w left of this thread's chunk
   for (int i0 = beg; i0 < end; i0 += 8) {
     float x[8];
-    bm_logits8(row, i0, V, vec, x);
+    logits8(row, i0, V, vec, x);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       if (i0 + e >= V) continue;
-      const unsigned key = bm_key16(x[e]);
+      const unsigned key = key16(x[e]);
       if (key > key_w || (key == key_w && eq_rank++ < need)) {
         const int slot = atomicAdd(&s_n, 1);
         if (slot < BM_MAXW) { s_x[slot] = x[e]; s_i[slot] = i0 + e; }
@@ -196,10 +156,10 @@ __global__ void __launch_bounds__(256) beam_topw_kernel(const bf16_t* __restrict
     if (tid < W) {
       const float x = s_x[tid];
       const int i = s_i[tid];
-      const unsigned key = bm_key16(x);
+      const unsigned key = key16(x);
       int r = 0;
       for (int j = 0; j < W; ++j) {
-        const unsigned kj = bm_key16(s_x[j]);
+        const unsigned kj = key16(s_x[j]);
         r += (kj > key || (kj == key && s_i[j] < i)) ? 1 : 0;
       }
       ct[r] = i;
@@ -326,8 +286,6 @@ __global__ void __launch_bounds__(256) beam_reorder_kernel(BeamArgs a, int* pos_
 }  // namespace jdt
 using namespace jdt;
 
-static bool beam_misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
-
 // Shape codes of both launchers, returned before anything is launched: -2 a null pointer, -3 a head
 // dim other than 64, -4 S_max outside 1..32768, -5 a bad size (V < 1, ld < V, B < 0, H < 1, a grid past
 // the launch limits), -6 a cache base that is not 16-byte aligned, -12 W outside 1..8, -13 B % W != 0,
@@ -345,7 +303,7 @@ JDT_API int jdt_beam_topw(const void* logits, long ld, int B, int V, int W, cons
   if (eos_id >= V) return -15;
   if (S_max < 1 || S_max > BM_SMAX) return -4;
   if (B == 0) return 0;
-  const int vec = (V % 8 == 0) && (ld % 8 == 0) && !beam_misaligned16(logits);
+  const int vec = (V % 8 == 0) && (ld % 8 == 0) && !misaligned16(logits);
   hipLaunchKernelGGL(beam_topw_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream),
                      static_cast<const bf16_t*>(logits), ld, V, W, score, done, eos_id, cand_tok, cand_score, pos,
                      S_max, vec);
@@ -370,7 +328,7 @@ JDT_API int jdt_beam_reorder(const int* cand_tok, const float* cand_score, void*
   if (S_max < 1 || S_max > BM_SMAX) return -4;
   for (int i = 0; i < n_caches; ++i) {
     if (!caches_host[i]) return -2;
-    if (beam_misaligned16(caches_host[i])) return -6;
+    if (misaligned16(caches_host[i])) return -6;
   }
   if (B == 0) return 0;
   const long gy = (long)(B / W) * H, gx = (S_max + BM_ROWS - 1) / BM_ROWS, gz = (long)n_caches + 1;

@@ -36,6 +36,24 @@ __device__ __forceinline__ bf16_t f2bf(float f) {
 }
 __device__ __forceinline__ float round_bf(float f) { return bf2f(f2bf(f)); }
 
+// 16 bytes = 8 bf16 -> 8 floats (word j holds elements 2j, low half, and 2j + 1)
+__device__ __forceinline__ void unpack8(const u32x4& r, float (&x)[8]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    x[2 * j] = bf2f((bf16_t)(r[j] & 0xffff));
+    x[2 * j + 1] = bf2f((bf16_t)(r[j] >> 16));
+  }
+}
+// acc + dot of two such rows, in a fixed order: word by word, each word as lo * lo + hi * hi
+__device__ __forceinline__ float dot8(const u32x4& a, const u32x4& b, float acc) {
+  float x[8], y[8];
+  unpack8(a, x);
+  unpack8(b, y);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc += x[2 * j] * y[2 * j] + x[2 * j + 1] * y[2 * j + 1];
+  return acc;
+}
+
 // ---------------------------------------------------------------- FSDP staged gradient bucket
 // A producer kernel of the FSDP step (mlp2_bwd / md_bwd mode 0) writes each full-layout
 // gradient element straight into this rank's xGMI data buffer, in the packed layout of
@@ -487,3 +505,6 @@ __device__ __forceinline__ void tx_tile(const TxArgs* X, int T, unsigned epoch, 
 }  // namespace jdt
 
 #define HIP_LAUNCH_CHECK() (int)hipGetLastError()
+
+// host: the launchers' check of a pointer the kernel reads with 16-byte loads
+static inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }

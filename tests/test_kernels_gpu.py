@@ -1023,6 +1023,56 @@ def test_attn128_vs_autograd_and_flash(B, S, H, causal):
     _close(o_n, res[0][0], rtol=2e-2, atol=2e-2)
 
 
+@pytest.mark.parametrize("S", [17, 64, 65, 200])   # a partial tile, an exact one, a seam, more than 128
+def test_append_at_empty_cache_is_the_flash_forward(S):
+    """One tile body (csrc/attn_tile.h): appending S tokens to an empty cache gives the bits of the
+    causal training forward.  With pos = 0 both kernels visit the same key tiles (kend =
+    min(S, q0 + 64)), stage the same LDS images (rows >= kend zero) and mask the same keys."""
+    from jax_distributed_tuts_amd.ops import _lib
+
+    B, H = 2, 2
+    qkv = _mk((B * S, 3 * H * 64), torch.bfloat16, seed=81).to(DEV)
+    kc = torch.full((B, H, S + 8, 64), 7.0, dtype=torch.bfloat16, device=DEV)   # sentinel: never read
+    vc = kc.clone()
+    try:
+        _lib.lib().jdt_flash_set_attn128(0)
+        o_f, _ = kern.attention_fwd(qkv, B, S, H, causal=True)
+    finally:
+        _lib.lib().jdt_flash_set_attn128(1)
+    o_a = kern.attention_append(qkv, kc, vc, torch.zeros(1, dtype=torch.int32, device=DEV), H, S)
+    assert torch.equal(o_a, o_f)
+
+
+@pytest.mark.parametrize("S", [40, 64, 100, 128])
+@pytest.mark.parametrize("causal", [True, False])
+def test_flash_bwd_head_and_key_block_kernels_agree(S, causal):
+    """One backward tile body (csrc/attn_tile.h) under two loops: the whole-head kernel and the
+    key-block kernel give bit-equal dK / dV (the same wave, keys and query-tile order: the same MFMA
+    chain) and, with one key block (S <= 64: each dQ element is one addend onto zero), bit-equal dQ;
+    above that the key-block kernel's dQ is a sum of fp32 atomics."""
+    from jax_distributed_tuts_amd.ops import _lib
+
+    B, H = 2, 2
+    d = H * 64
+    qkv = _mk((B * S, 3 * d), torch.bfloat16, seed=83).to(DEV)
+    do = _mk((B * S, d), torch.bfloat16, seed=84).to(DEV)
+    g = {}
+    try:
+        _lib.lib().jdt_flash_set_attn128(0)
+        o, lse = kern.attention_fwd(qkv, B, S, H, causal=causal)
+        for head in (1, 0):
+            _lib.lib().jdt_flash_set_head(head)
+            g[head] = kern.attention_bwd(do, qkv, lse, B, S, H, o=o, causal=causal).view(B * S, 3, d)
+    finally:
+        _lib.lib().jdt_flash_set_head(1)
+        _lib.lib().jdt_flash_set_attn128(1)
+    assert torch.equal(g[1][:, 1:], g[0][:, 1:])
+    if S <= 64:
+        assert torch.equal(g[1][:, 0], g[0][:, 0])
+    else:
+        _close(g[1][:, 0], g[0][:, 0], rtol=3e-2, atol=3e-2)
+
+
 @pytest.mark.parametrize("fused", [True, False])
 def test_fsdp_graph_replay_matches_eager(fused):
     """FSDP (world 1) captured as single- and multi-step hipGraphs == eager steps."""
