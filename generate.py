@@ -8,6 +8,7 @@ one captured decode step replayed per token).
     python generate.py --batch 3 --prompt-lens 5,16,9 --temperature 0.8 --top-k 50 --top-p 0.9 --eos-id 7
     python generate.py --seq-len 1024 --prompt-len 900 --max-new-tokens 100   # a 1024-row KV cache
     python generate.py --seq-len 1024 --prompt-len 900 --prefill-chunk 256    # chunked prefill into the cache
+    python generate.py --seq-len 4096 --prompt-len 4000 --prefill-chunk 64 --split-append   # split-KV append
     python generate.py --beams 4 --length-penalty 1.0 --eos-id 7              # beam search, 4 hypotheses per prompt
 
 Runs the HIP kernels on a GPU and the torch reference paths on CPU tensors when none is
@@ -17,7 +18,9 @@ present.  The prompt is the first ``--prompt-len`` tokens of ``lm_batch``'s sequ
 printed up to its own final length.  ``--seq-len`` builds the LM with that many learned
 positions (default 128); up to 32768 the decode attention stays on the HIP kernels (split-KV
 past 128 cache rows).  ``--prefill-chunk N`` fills the cache through the append kernels in slices
-of N prompt rows instead of one pass of the training forward.  ``--beams W`` (1..8) runs a beam search
+of N prompt rows instead of one pass of the training forward; ``--split-append`` (only with
+``--prefill-chunk``) runs them through the split-KV append attention, meant for small N and deep
+caches.  ``--beams W`` (1..8) runs a beam search
 instead of sampling: ``--batch`` prompts with W hypotheses each (a generator of batch * W rows), printed
 best first with their scores, ranked by ``log-probability / length ** --length-penalty``.
 Not covered: beams over ragged prompts, diverse or constrained beam search, repetition penalties,
@@ -57,11 +60,17 @@ def parse_args(argv=None):
     ap.add_argument("--prefill-chunk", type=int, default=None, metavar="N",
                     help="chunked prefill: the prompt goes into the cache in slices of N rows "
                          "(default: one pass of the training forward)")
+    ap.add_argument("--split-append", action="store_true",
+                    help="with --prefill-chunk: the chunked prefill runs the split-KV append attention "
+                         "(one workgroup per 512-key span of the cache and a combine launch)")
     ap.add_argument("--beams", type=int, default=0, metavar="W",
                     help="beam search with W hypotheses per prompt (1..8) instead of sampling")
     ap.add_argument("--length-penalty", type=float, default=0.0, metavar="A",
                     help="beam ranking: log-probability / generated length ** A (0: the raw log-probability)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.split_append and args.prefill_chunk is None:
+        ap.error("--split-append needs --prefill-chunk N: only the chunked prefill appends to the cache")
+    return args
 
 
 def beam_main(args, tr, prompt, dev):
@@ -69,7 +78,7 @@ def beam_main(args, tr, prompt, dev):
         raise SystemExit("--beams is a deterministic search over prompts of one length: it takes none of "
                          "--prompt-lens, --temperature, --top-k, --top-p")
     W = args.beams
-    gen = Generator(tr.state.apply_fn, tr.state.params, args.batch * W, dev)
+    gen = Generator(tr.state.apply_fn, tr.state.params, args.batch * W, dev, split_append=args.split_append)
     sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
     kw = dict(eos_id=args.eos_id, length_penalty=args.length_penalty, capture=not args.eager,
               prefill_chunk=args.prefill_chunk)
@@ -115,7 +124,7 @@ def main(args):
     prompt = data.inputs[:args.batch, :args.prompt_len].contiguous().to(dev)
     if args.beams:
         return beam_main(args, tr, prompt, dev)
-    gen = Generator(tr.state.apply_fn, tr.state.params, args.batch, dev)
+    gen = Generator(tr.state.apply_fn, tr.state.params, args.batch, dev, split_append=args.split_append)
     sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
     kw = dict(temperature=args.temperature, seed=args.seed, capture=not args.eager, prompt_lens=lens,
               top_k=args.top_k, top_p=args.top_p, eos_id=args.eos_id, prefill_chunk=args.prefill_chunk)

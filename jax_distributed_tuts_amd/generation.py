@@ -39,6 +39,15 @@ the same position.  ``extend(tokens)`` appends to a live cache: a second turn af
 teacher forcing a block of tokens, or scoring a continuation (``logits=True``).  The bits a
 token's attention output gets do not depend on how the tokens were cut into calls or slices.
 
+Split append (``Generator(..., split_append=True)``, opt-in): a slice of a few rows against a deep
+cache is, in the one launch, a handful of workgroups that each walk the whole cache below their
+query tile.  The split pair of launches gives every 512-key span of absolute cache rows a
+workgroup of its own per query tile and folds the spans' partials in a combine launch, the way
+the split-KV decode does for one query; ``KVCache.append_ws`` holds the partials, ``advance``
+sizes it for its largest slice before the loop (from ``n`` and ``chunk``: the position is not read)
+and every layer reuses it.  The caches are bit for bit the one launch's, tokens below row 512 get
+its bits, and the bits of a deeper token still do not depend on how the tokens were cut.
+
 Beam search: ``beam_search(prompt [G, P], n, num_beams=W)`` on a generator of batch G * W keeps W
 hypotheses per prompt; batch row g * W + j is beam slot j of group g, and the position is the shared
 one.  A step is the decode step above followed by two launches of csrc/beam.hip instead of the
@@ -53,10 +62,10 @@ Out of scope: beams over ragged prompts (per-row positions), diverse or constrai
 beam cache that re-routes through an indirection table instead of copying, sharing the prompt's
 cache rows between the beams of a group, repetition penalties, sequences longer than ``seq_len`` (the
 learned positions end there), multi-GPU or pipeline-split generation, paged or compacted
-caches, ``generate()`` continuing a live cache, a split-KV append kernel (an append workgroup
-walks the whole cache above its query tile), removing finished rows from the batch, and head
-dims other than 64 or caches past 32768 rows on the HIP path.  Chunked prefill is opt-in: the
-default ``prefill`` is still the training forward.
+caches, ``generate()`` continuing a live cache, split append as the default, a span size chosen
+per shape (the spans are absolute so that the cut does not change the bits), removing finished
+rows from the batch, and head dims other than 64 or caches past 32768 rows on the HIP path.
+Chunked prefill is opt-in: the default ``prefill`` is still the training forward.
 """
 from __future__ import annotations
 
@@ -78,7 +87,14 @@ class KVCache:
     ``pos_rows`` int32[B] and ``end`` int32[B] (one past the last token index a row may hold);
     ``per_row`` says which position tensor is live (``live_pos``): ``pos`` by default.
     ``split_ws``: the split-KV decode attention's partials, fp32 ``[B * H, ceil(seq_len / 128),
-    66]`` (one buffer, reused layer after layer), or ``None`` when ``seq_len <= 128``."""
+    66]`` (one buffer, reused layer after layer), or ``None`` when ``seq_len <= 128``.
+    ``append_ws``: the split-KV append attention's partials, flat fp32 of at least
+    ``ops.kernels.attention_append_ws_floats(B, H, C, seq_len)`` words for the largest slice size C
+    appended so far (one buffer, reused layer after layer), or ``None``: ``append_chunk`` then runs the
+    one-launch kernel.  Only ``Generator(split_append=True)`` allocates it, on first use and again
+    when a larger slice needs more.  Size: 16.5 KiB (64 rows x 66 words) per (batch x head, 64-row
+    query tile, 512-key span) -- 8.3 MiB at B = 1, H = 8, chunk 64 and ``seq_len`` 32768, and it
+    scales with the chunk and the batch."""
 
     def __init__(self, cfg: TransformerConfig, batch: int, device):
         H, Dh = cfg.n_heads, cfg.d_model // cfg.n_heads
@@ -96,6 +112,7 @@ class KVCache:
         if cfg.seq_len > K.AD_CHUNK_ROWS:
             chunks = (cfg.seq_len + K.AD_CHUNK_ROWS - 1) // K.AD_CHUNK_ROWS
             self.split_ws = torch.zeros(batch * H, chunks, K.AD_SLOT_FLOATS, dtype=torch.float32, device=device)
+        self.append_ws: Optional[torch.Tensor] = None
         self._history_ptrs = None
 
     @property
@@ -135,15 +152,19 @@ class BeamState:
 
 class Generator:
     """Generation with a full (un-split) ``TransformerLM`` and its parameters ``P`` for a
-    fixed batch of ``batch`` sequences on ``device``."""
+    fixed batch of ``batch`` sequences on ``device``.  ``split_append`` (opt-in): everything that
+    appends to the cache -- ``prefill(chunk=)``, ``extend``, ``generate(prefill_chunk=)``,
+    ``beam_search(prefill_chunk=)`` -- runs the split-KV append attention (``KVCache.append_ws``
+    holds its partials) instead of the one-launch kernel."""
 
-    def __init__(self, model: TransformerLM, P: FlatParams, batch: int, device):
+    def __init__(self, model: TransformerLM, P: FlatParams, batch: int, device, split_append: bool = False):
         if not (model.has_embed and model.has_head and list(model.layers) == list(range(model.cfg.n_layers))):
             raise ValueError("Generator needs the full model (embedding, every layer and the head): "
                              "pipeline-split stages cannot generate")
         self.model, self.P, self.batch, self.device = model, P, int(batch), torch.device(device)
         self.kv = KVCache(model.cfg, self.batch, self.device)
-        self.x = torch.zeros(self.batch, model.cfg.d_model, dtype=torch.bfloat16, device=self.device)
+        self.split_append = bool(split_append)
+        self.x =torch.zeros(self.batch, model.cfg.d_model, dtype=torch.bfloat16, device=self.device)
         self.temperature, self.seed = 0.0, 0
         self.top_k, self.top_p, self.eos_id = 0, 1.0, -1
         self.logits: Optional[torch.Tensor] = None   # the last step's logits [B, vocab]
@@ -236,7 +257,8 @@ class Generator:
         int or, per-row mode only, an int tensor [B] (slice j of row b then holds
         ``clamp(n_b - j * chunk, 0, chunk)`` tokens).  The position is never read on the host: the
         counts come from ``n``, and the caller answers for ``pos + n <= seq_len`` (a slice that would
-        pass the end of the cache writes nothing, but the position still advances).
+        pass the end of the cache writes nothing, but the position still advances).  With
+        ``split_append`` set, ``kv.append_ws`` is first made to hold the largest slice's partials.
 
         ``logits=True``: returns the logits [B, vocab] of each row's last processed token (a row
         with nothing to process: of a zero vector); their block outputs are gathered before
@@ -261,6 +283,11 @@ class Generator:
         if x is None:   # once per chunk size, zero-initialised: rows past a count stay finite
             x = self._chunk_bufs[chunk] = torch.zeros(B * chunk, c.d_model, dtype=torch.bfloat16, device=self.device)
         last = torch.zeros(B, c.d_model, dtype=torch.bfloat16, device=self.device) if logits else None
+        if self.split_append and max(nb) > 0:
+            # the largest slice's partials; an outgrown buffer is replaced, a larger one is kept
+            need = K.attention_append_ws_floats(B, c.n_heads, min(chunk, max(nb)), c.seq_len)
+            if kv.append_ws is None or kv.append_ws.numel() < need:
+                kv.append_ws = torch.empty(need, dtype=torch.float32, device=self.device)
         for lo in range(0, max(nb), chunk):
             C = min(chunk, max(nb) - lo)
             cnt = [min(max(v - lo, 0), C) for v in nb]

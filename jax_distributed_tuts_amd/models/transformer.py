@@ -249,7 +249,9 @@ class TransformerLM:
         ``attention_decode``.  ``x`` [B*C, d_model] bf16: row b*C + i is the embedded token at
         position pos + i (``ops.kernels.embed_append``); ``count`` int32[B] (per-row cache only): the
         tokens sequence b really appends, rows past it are computed on whatever ``x`` holds and mean
-        nothing.  The position is the cache's live tensor and is only read.  ``head=False`` skips
+        nothing.  The position is the cache's live tensor and is only read.  A ``kv.append_ws`` that is
+        not ``None`` (``Generator(split_append=True)``) is handed to ``attention_append`` as its ``ws``:
+        the split-KV pair of launches per layer, one buffer for every layer.  ``head=False`` skips
         ``ln_f`` and the head entirely and returns the last block's output [B*C, d_model];
         ``head=True`` returns the logits [B*C, vocab] (``lm_head``)."""
         if not (self.has_embed and self.has_head):
@@ -265,7 +267,8 @@ class TransformerLM:
             # per-row counts: rows past a sequence's count keep the zeros (finite inputs for the GEMMs below)
             mk = torch.empty if count is None else torch.zeros
             o = mk(h.shape[0], c.d_model, dtype=torch.bfloat16, device=h.device)
-            K.attention_append(qkv, kv.k[l], kv.v[l], pos, c.n_heads, C, count=count, out=o)
+            K.attention_append(qkv, kv.k[l], kv.v[l], pos, c.n_heads, C, count=count, out=o,
+                               ws=getattr(kv, "append_ws", None))
             x2 = K.gemm(o, P.s(f"{b}/attn/out/kernel"), bias=P.s(f"{b}/attn/out/bias"), resid=h)
             z1 = torch.empty(x2.shape[0], c.d_ff, dtype=torch.bfloat16, device=x2.device)
             u, _, _, _ = K.ln_gemm(x2, P.p(f"{b}/ln2/scale"), P.p(f"{b}/ln2/bias"), P.s(f"{b}/mlp/fc1/kernel"),

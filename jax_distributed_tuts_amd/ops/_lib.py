@@ -140,8 +140,14 @@ _SIGS = {
                                 c_float, c_void_p]),
     "jdt_attn_append_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                      c_int, c_int, c_float, c_void_p]),
+    # the split-KV pair of launches: (qkv, k_cache, v_cache, o, pos, ws, ws_floats, B, C, H, Dh, S_max, scale,
+    # stream); per row: (..., pos, count, ws, ...)
+    "jdt_attn_append_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int,
+                                      c_int, c_int, c_int, c_float, c_void_p]),
+    "jdt_attn_append_split_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     # (tokens, wte, wpe, out, pos, B, C, S_max, d, vocab, stream); per row: (..., pos, count, B, ...)
-    "jdt_embed_append": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+    "jdt_embed_append":(c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                  c_void_p]),
     "jdt_embed_append_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                       c_int, c_int, c_void_p]),

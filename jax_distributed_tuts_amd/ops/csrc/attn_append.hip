@@ -28,21 +28,47 @@
 // The next key tile's global loads are issued into registers before the current tile's MFMA
 // work and stored to LDS after it, so their latency overlaps the compute; the LDS store of a
 // chunk is attn_tile.h's (transposed V: scalar LDS writes).
+//
+// Split-KV (the ``_split`` launchers, opt-in): at B = 1 the grid above is a handful of workgroups
+// that each walk the whole cache below their query tile.  The split pair spreads one query tile's
+// keys over workgroups instead, as attn_decode.hip does for one query: two launches on one stream,
+// the kernel boundary is the hand-off (no in-launch tickets, flags or waits).
+//   * split launch (attn_append_kernel<ROWS, true>: the same kernel text, as attn_decode_kernel's
+//     SPLIT), grid (ceil(C/64), B*H, ceil(S_max/AP_SPAN)): workgroup (qt, bh, s) runs the
+//     body over the key tiles of span s only, the ABSOLUTE cache rows [s*AP_SPAN, (s+1)*AP_SPAN)
+//     below p + qn, and instead of normalising stores each row's (m, l, unnormalised o[64]) into
+//     workspace slot (bh, qt, s, row).  A span that starts at or past p + qn has no workgroup work
+//     and no partial.  Only the s == 0 workgroup (it always exists) writes the tile's k / v rows
+//     into the cache; nobody reads what another workgroup of the launch writes.
+//   * combine launch, grid (ceil(C/64), B*H): row i with t = p + i folds the partials of spans
+//     0 .. t / AP_SPAN in increasing order with the decode combine's expressions: M = max m_s,
+//     L = sum l_s e^(m_s - M), o = (sum o_s e^(m_s - M)) * (1 / L) as bf16.  Exactly those slots are
+//     read -- each was written by this call's split launch, so stale (even NaN) workspace contents
+//     are harmless.  One span: e^0 = 1 and o_0 * (1 / l_0), the bits of the one-launch kernel.
+// The spans are absolute and a fully masked tile is an exact no-op, so the cut invariance above
+// holds for the split pair too; the caches come out bit for bit as from the one-launch kernel.
 #include "attn_tile.h"
 
 #include <limits.h>
+
+#include <type_traits>
 
 namespace jdt {
 
 constexpr int AP_SMAX = 32768;      // cache rows per head the launchers accept
 constexpr int AP_CMAX = 1024;       // new tokens per sequence and call
+constexpr int AP_SPAN = 512;        // keys per workgroup of the split launch: 8 key tiles, absolute cache rows
+constexpr int AP_SLOT = 2 + AT_D;   // fp32 words of a row's partial: max, sum, unnormalised o[64]
+constexpr int AP_CB = 8;            // spans the combine loads at a time
 
-template <bool ROWS>
-__global__ void __launch_bounds__(256) attn_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
-                                                         bf16_t* __restrict__ vc, bf16_t* __restrict__ out,
-                                                         const int* __restrict__ pos_ptr,
-                                                         const int* __restrict__ count, int C, int H, int S_max,
-                                                         float scale) {
+// One body for both launches, as attn_decode_kernel.  SPLIT (the split launch): blockIdx.z is the
+// span and ``out`` is the fp32 workspace instead of o, so <ROWS, false> keeps the one-launch
+// kernel's arguments and instruction stream.
+template <bool ROWS, bool SPLIT>
+__global__ void __launch_bounds__(256)
+attn_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+                   std::conditional_t<SPLIT, float, bf16_t>* __restrict__ out, const int* __restrict__ pos_ptr,
+                   const int* __restrict__ count, int C, int H, int S_max, float scale) {
   __shared__ __attribute__((aligned(16))) bf16_t Ks[AT_T * AT_LD];
   __shared__ __attribute__((aligned(16))) bf16_t Vt[AT_D * AT_LD];
   __shared__ __attribute__((aligned(16))) bf16_t Ps[4][16 * AT_LD];
@@ -56,16 +82,20 @@ __global__ void __launch_bounds__(256) attn_append_kernel(const bf16_t* __restri
   if (q0 >= n) return;
   const int qn = min(q0 + AT_T, n);   // one past this workgroup's last token (chunk index)
   const int kend = p + qn;            // one past the last key any of its queries sees (<= S_max)
+  // SPLIT: the span's key tiles [kbeg, kstop) only; a span at or past kend: no partial, its slot is never read
+  const int kbeg = SPLIT ? (int)blockIdx.z * AP_SPAN : 0;
+  if (SPLIT && kbeg >= kend) return;
+  const int kstop = SPLIT ? min(kbeg + AP_SPAN, kend) : kend;
   const int d = H * AT_D;
   const long ld3 = 3L * d;
   const bf16_t* base = qkv + (long)b * C * ld3 + h * AT_D;   // token 0's q; + d: k; + 2 d: v
   bf16_t* Kh = kc + (long)bh * S_max * AT_D;
   bf16_t* Vh = vc + (long)bh * S_max * AT_D;
 
-  // this query tile's k / v rows -> cache rows p + q0 .. p + qn - 1
+  // this query tile's k / v rows -> cache rows p + q0 .. p + qn - 1 (SPLIT: span 0's workgroup alone)
   for (int c = threadIdx.x; c < AT_T * AT_D / 8; c += 256) {
     const int i = q0 + (c >> 3), dc = (c & 7) * 8;
-    if (i < qn) {
+    if (i < qn && (!SPLIT || blockIdx.z == 0)) {
       const bf16_t* src = base + (long)i * ld3 + dc;
       *reinterpret_cast<u32x4*>(Kh + (long)(p + i) * AT_D + dc) = *reinterpret_cast<const u32x4*>(src + d);
       *reinterpret_cast<u32x4*>(Vh + (long)(p + i) * AT_D + dc) = *reinterpret_cast<const u32x4*>(src + 2 * d);
@@ -110,20 +140,95 @@ __global__ void __launch_bounds__(256) attn_append_kernel(const bf16_t* __restri
 #pragma unroll
   for (int e = 0; e < 4; ++e) last[e] = p + q0 + w * 16 + (lane >> 4) * 4 + e;
 
-  fetch(0);
-  for (int k0 = 0; k0 < kend; k0 += AT_T) {
+  fetch(kbeg);
+  for (int k0 = kbeg; k0 < kstop; k0 += AT_T) {
     __syncthreads();   // the previous tile's readers are done with Ks / Vt
     stage();
     __syncthreads();
-    if (k0 + AT_T < kend) fetch(k0 + AT_T);
+    if (k0 + AT_T < kstop) fetch(k0 + AT_T);
     fwd_tile_step(Ks, Vt, Ps[w], qf, scale, k0, last, m, l, o);
   }
+  // SPLIT: the query tile's 64 slots of span blockIdx.z; a row whose queries all lie below the span
+  // leaves (-inf, 0, 0), which the combine never reads
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int i = q0 + w * 16 + (lane >> 4) * 4 + e;
     if (i >= qn) continue;
-    fwd_store_row(out + ((long)b * C + i) * d + h * AT_D, o, e, l[e]);
+    if constexpr (SPLIT) {
+      float* slot = out + (((long)bh * gridDim.x + blockIdx.x) * gridDim.z + blockIdx.z) * (AT_T * AP_SLOT) +
+                    (i - q0) * AP_SLOT;
+      if ((lane & 15) == 0) {   // m and l are the same in the row's 16 lanes
+        slot[0] = m[e];
+        slot[1] = l[e];
+      }
+#pragma unroll
+      for (int nt = 0; nt < 4; ++nt) slot[2 + nt * 16 + (lane & 15)] = o[nt][e];
+    } else {
+      fwd_store_row(out + ((long)b * C + i) * d + h * AT_D, o, e, l[e]);
+    }
   }
+}
+
+// The combine launch: grid (ceil(C/64), B*H), 1024 threads = 64 rows x 16 lanes; lane j of row r owns
+// columns 2j, 2j + 1, 32 + 2j and 33 + 2j (two 8-byte loads per partial: a slot is 8-byte aligned).
+// Row i of the chunk (t = p + i) folds spans 0 .. t / AP_SPAN in increasing order, AP_CB spans' loads
+// in flight at a time (a block's tail past the last span re-reads that span and is not folded); the
+// expressions are attn_decode_combine_kernel's.  Rows i >= n of o and out-of-range sequences are
+// left alone.
+template <bool ROWS>
+__global__ void __launch_bounds__(1024) attn_append_combine_kernel(const float* __restrict__ ws,
+                                                                  bf16_t* __restrict__ out,
+                                                                  const int* __restrict__ pos_ptr,
+                                                                  const int* __restrict__ count, int C, int H,
+                                                                  int S_max, int n_spans) {
+  const int bh = blockIdx.y, b = bh / H, h = bh % H;
+  const int p = pos_ptr[ROWS ? b : 0];
+  const int n = ROWS ? count[b] : C;
+  if (n < 0 || n > C || p < 0 || p > S_max - n) return;
+  const int r = threadIdx.x >> 4, j = threadIdx.x & 15;
+  const int i = blockIdx.x * AT_T + r;
+  if (i >= n) return;   // the 16 lanes of a row leave together; no barrier below
+  const int last = (p + i) / AP_SPAN;   // < n_spans: p + i < S_max
+  constexpr long SPAN_STRIDE = AT_T * AP_SLOT;
+  const float* slot = ws + ((long)bh * gridDim.x + blockIdx.x) * n_spans * SPAN_STRIDE + r * AP_SLOT;
+  float M = -INFINITY;
+  for (int s = j; s <= last; s += 16) M = fmaxf(M, slot[s * SPAN_STRIDE]);
+#pragma unroll
+  for (int off = 1; off < 16; off <<= 1) M = fmaxf(M, __shfl_xor(M, off, 64));   // a max does not depend on the order
+  const int c0 = 2 + 2 * j, c1 = 2 + 32 + 2 * j;
+  float wgt = __expf(slot[0] - M);
+  float L = slot[1] * wgt;
+  float2 a0 = *reinterpret_cast<const float2*>(slot + c0), a1 = *reinterpret_cast<const float2*>(slot + c1);
+  float acc[4] = {a0.x * wgt, a0.y * wgt, a1.x * wgt, a1.y * wgt};
+  for (int s0 = 1; s0 <= last; s0 += AP_CB) {
+    float pm[AP_CB], pl[AP_CB];
+    float2 po0[AP_CB], po1[AP_CB];
+#pragma unroll
+    for (int k = 0; k < AP_CB; ++k) {
+      const float* s = slot + min(s0 + k, last) * SPAN_STRIDE;
+      pm[k] = s[0];
+      pl[k] = s[1];
+      po0[k] = *reinterpret_cast<const float2*>(s + c0);
+      po1[k] = *reinterpret_cast<const float2*>(s + c1);
+    }
+#pragma unroll
+    for (int k = 0; k < AP_CB; ++k) {
+      if (s0 + k <= last) {
+        wgt = __expf(pm[k] - M);
+        L += pl[k] * wgt;
+        acc[0] += po0[k].x * wgt;
+        acc[1] += po0[k].y * wgt;
+        acc[2] += po1[k].x * wgt;
+        acc[3] += po1[k].y * wgt;
+      }
+    }
+  }
+  const float inv = 1.f / L;
+  bf16_t* row = out + ((long)b * C + i) * (H * AT_D) + h * AT_D;
+  row[2 * j] = f2bf(acc[0] * inv);
+  row[2 * j + 1] = f2bf(acc[1] * inv);
+  row[32 + 2 * j] = f2bf(acc[2] * inv);
+  row[33 + 2 * j] = f2bf(acc[3] * inv);
 }
 
 }  // namespace jdt
@@ -141,7 +246,7 @@ static int attn_append_launch(const void* qkv, void* k_cache, void* v_cache, voi
   if (!qkv || !k_cache || !v_cache || !o || !pos || (ROWS && !count)) return -2;
   if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
   if (B == 0) return 0;
-  hipLaunchKernelGGL(attn_append_kernel<ROWS>, dim3((C + AT_T - 1) / AT_T, B * H), dim3(256), 0,
+  hipLaunchKernelGGL((attn_append_kernel<ROWS, false>), dim3((C + AT_T - 1) / AT_T, B * H), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(k_cache),
                      static_cast<bf16_t*>(v_cache), static_cast<bf16_t*>(o), pos, count, C, H, S_max, scale);
   return HIP_LAUNCH_CHECK();
@@ -158,4 +263,47 @@ JDT_API int jdt_attn_append(const void* qkv, void* k_cache, void* v_cache, void*
 JDT_API int jdt_attn_append_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos,
                                  const int* count, int B, int C, int H, int Dh, int S_max, float scale, void* stream) {
   return attn_append_launch<true>(qkv, k_cache, v_cache, o, pos, count, B, C, H, Dh, S_max, scale, stream);
+}
+
+// Split-KV: the split launch, then the combine on the same stream.  The checks and codes of
+// attn_append_launch, plus -2 for a null ws and -10 for a workspace below B * H * ceil(C / 64) *
+// ceil(S_max / 512) * 64 * 66 floats; everything is checked before anything is launched.
+template <bool ROWS>
+static int attn_append_split_launch(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos,
+                                    const int* count, float* ws, long ws_floats, int B, int C, int H, int Dh, int S_max,
+                                    float scale, void* stream) {
+  if (Dh != AT_D) return -3;
+  if (S_max < 1 || S_max > AP_SMAX) return -4;
+  if (C < 1 || C > AP_CMAX) return -11;
+  if (B < 0 || H < 1 || (long)B * H > 65535) return -5;
+  if (!qkv || !k_cache || !v_cache || !o || !pos || (ROWS && !count) || !ws) return -2;
+  if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
+  const int n_qt = (C + AT_T - 1) / AT_T, n_spans = (S_max + AP_SPAN - 1) / AP_SPAN;
+  if (ws_floats < (long)B * H * n_qt * n_spans * AT_T * AP_SLOT) return -10;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL((attn_append_kernel<ROWS, true>), dim3(n_qt, B * H, n_spans), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(k_cache),
+                     static_cast<bf16_t*>(v_cache), ws, pos, count, C, H, S_max, scale);
+  const int rc = HIP_LAUNCH_CHECK();
+  if (rc) return rc;
+  hipLaunchKernelGGL(attn_append_combine_kernel<ROWS>, dim3(n_qt, B * H), dim3(1024), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const float*>(ws), static_cast<bf16_t*>(o), pos,
+                     count, C, H, S_max, n_spans);
+  return HIP_LAUNCH_CHECK();
+}
+
+// jdt_attn_append through the split-KV pair: ws is fp32 scratch of ws_floats >= B * H * ceil(C / 64) *
+// ceil(S_max / 512) * 64 * 66 words (any contents; one slot per row of a workgroup of the split launch)
+JDT_API int jdt_attn_append_split(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, float* ws,
+                                  long ws_floats, int B, int C, int H, int Dh, int S_max, float scale, void* stream) {
+  return attn_append_split_launch<false>(qkv, k_cache, v_cache, o, pos, nullptr, ws, ws_floats, B, C, H, Dh, S_max,
+                                         scale, stream);
+}
+
+// as jdt_attn_append_split with one position and one token count per sequence: pos int32[B], count int32[B]
+JDT_API int jdt_attn_append_split_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos,
+                                       const int* count, float* ws, long ws_floats, int B, int C, int H, int Dh,
+                                       int S_max, float scale, void* stream) {
+  return attn_append_split_launch<true>(qkv, k_cache, v_cache, o, pos, count, ws, ws_floats, B, C, H, Dh, S_max,
+                                        scale, stream);
 }

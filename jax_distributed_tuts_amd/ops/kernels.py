@@ -1140,6 +1140,17 @@ def embed_decode(tokens: torch.Tensor, wte: torch.Tensor, wpe: torch.Tensor, pos
 
 # ----------------------------------------------------------------------------- append (C tokens per sequence)
 AP_MAX_ROWS, AP_MAX_CHUNK = 32768, 1024   # envelope of jdt_attn_append (csrc/attn_append.hip AP_SMAX, AP_CMAX)
+# split-KV append (jdt_attn_append_split): keys per workgroup (absolute cache rows), fp32 words of a
+# row's partial (csrc/attn_append.hip AP_SPAN, AP_SLOT)
+AP_SPAN_ROWS, AP_SLOT_FLOATS = 512, 66
+AP_TILE_ROWS = 64   # query rows per workgroup (csrc/attn_tile.h AT_T)
+
+
+def attention_append_ws_floats(B: int, H: int, C: int, S_max: int) -> int:
+    """fp32 words of the split-KV append workspace: one partial per (batch x head, 64-row query
+    tile, 512-key span, row of the tile)."""
+    tiles, spans = (C + AP_TILE_ROWS - 1) // AP_TILE_ROWS, (S_max + AP_SPAN_ROWS - 1) // AP_SPAN_ROWS
+    return B * H * tiles * spans * AP_TILE_ROWS * AP_SLOT_FLOATS
 
 
 def _append_state(pos: torch.Tensor, count: Optional[torch.Tensor], B: int, C: int):
@@ -1182,7 +1193,8 @@ def _attention_append_torch(qkv, k_cache, v_cache, pos, H, C, count, rows, out):
 
 
 def attention_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, H: int,
-                     C: int, count: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     C: int, count: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                     ws: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``C`` new query tokens per sequence against a KV cache (chunked prefill, teacher forcing,
     scoring a continuation).  ``qkv`` [B*C, 3*H*Dh] bf16 (row b*C + i is token i of sequence b;
     q | k | v as in training), ``k_cache`` / ``v_cache`` [B, H, S_max, Dh] bf16 (one layer), ``pos``
@@ -1196,7 +1208,16 @@ def attention_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     position: for any).  GPU, Dh = 64, S_max <= 32768 and C <= 1024: one launch of
     csrc/attn_append.hip, which reads ``pos`` / ``count`` on the device; its bits for the token at
     absolute index t depend only on (q_t, K[0..t], V[0..t]), not on how the tokens were cut into
-    calls.  Other GPU shapes run the composed torch path (which syncs on ``pos``), as CPU tensors do."""
+    calls.  Other GPU shapes run the composed torch path (which syncs on ``pos``), as CPU tensors do.
+
+    ``ws`` (opt-in; ``None``: the one launch above): fp32 scratch of >= ``attention_append_ws_floats(B,
+    H, C, S_max)`` words with any contents.  On the HIP path it selects the split-KV pair of launches:
+    one workgroup per (query tile, 512-key span of absolute cache rows) leaves each row's
+    unnormalised partial in ``ws`` and a combine launch on the same stream folds a row's spans in
+    increasing order -- for a few new rows against a deep cache, where the one launch is a handful of
+    workgroups that each walk the whole cache.  The caches come out bit for bit as from the one
+    launch, so do the rows with ``p + i < 512``; deeper rows differ in rounding only, and their bits
+    still depend on (q_t, K[0..t], V[0..t]) alone.  The composed torch path ignores ``ws``."""
     T, d3 = qkv.shape
     d = d3 // 3
     Dh = d // H
@@ -1213,6 +1234,19 @@ def attention_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     for t in (qkv, k_cache, v_cache, out):
         assert t.is_contiguous() and t.dtype == torch.bfloat16
     scale = float(1.0 / (Dh ** 0.5))
+    if ws is not None:
+        assert ws.is_contiguous() and ws.dtype == torch.float32 and ws.device == qkv.device
+        assert ws.numel() >= attention_append_ws_floats(B, H, C, S_max), "ws is below attention_append_ws_floats"
+        if rows:
+            rc = _lib.lib().jdt_attn_append_split_rows(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos),
+                                                       _ptr(count), _ptr(ws), ws.numel(), B, C, H, Dh, S_max, scale,
+                                                       _lib.stream_ptr())
+            _lib.check(rc, "jdt_attn_append_split_rows")
+        else:
+            rc = _lib.lib().jdt_attn_append_split(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos),
+                                                  _ptr(ws), ws.numel(), B, C, H, Dh, S_max, scale, _lib.stream_ptr())
+            _lib.check(rc, "jdt_attn_append_split")
+        return out
     if rows:
         rc = _lib.lib().jdt_attn_append_rows(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos),
                                              _ptr(count), B, C, H, Dh, S_max, scale, _lib.stream_ptr())

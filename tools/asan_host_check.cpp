@@ -56,6 +56,11 @@ int jdt_attn_append(const void* qkv, void* k_cache, void* v_cache, void* o, cons
                     int S_max, float scale, void* stream);
 int jdt_attn_append_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, const int* count,
                          int B, int C, int H, int Dh, int S_max, float scale, void* stream);
+int jdt_attn_append_split(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, float* ws,
+                          long ws_floats, int B, int C, int H, int Dh, int S_max, float scale, void* stream);
+int jdt_attn_append_split_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos,
+                               const int* count, float* ws, long ws_floats, int B, int C, int H, int Dh, int S_max,
+                               float scale, void* stream);
 int jdt_embed_append(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos, int B, int C,
                      int S_max, int d, int vocab, void* stream);
 int jdt_embed_append_rows(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos,
@@ -216,6 +221,52 @@ int main() {
          "attn_append_rows rejects a misaligned qkv");
   EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, ip, ip, 0, 64, 2, 64, 320, .125f, nullptr) == 0,
          "attn_append_rows B = 0 is a no-op");
+  // split-KV append launchers: the same envelope, plus the workspace (1 x 2 x 1 query tile x 1 span x 64 x 66 floats)
+  const long big = 1L << 40;   // a workspace size no shape here exceeds
+  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 8448, 1, 64, 2, 32, 320, .125f, nullptr) == -3,
+         "attn_append_split rejects head dim 32");
+  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 8448, 1, 64, 2, 64, 0, .125f, nullptr) == -4,
+         "attn_append_split rejects S_max 0");
+  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, big, 1, 64, 2, 64, 32769, .125f, nullptr) == -4,
+         "attn_append_split rejects S_max 32769");
+  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 8448, 1, 0, 2, 64, 320, .125f, nullptr) == -11,
+         "attn_append_split rejects C 0");
+  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, big, 1, 1025, 2, 64, 320, .125f, nullptr) == -11,
+         "attn_append_split rejects C 1025");
+  EXPECT(jdt_attn_append_split(buf, buf, nullptr, buf, ip, fp, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_append_split rejects null");
+  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, nullptr, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_append_split rejects a null ws");
+  EXPECT(jdt_attn_append_split(buf, buf + 4, buf, buf, ip, fp, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
+         "attn_append_split rejects a misaligned cache");
+  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, big, 65536, 64, 1, 64, 320, .125f, nullptr) == -5,
+         "attn_append_split rejects B * H past the grid");
+  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 8447, 1, 64, 2, 64, 320, .125f, nullptr) == -10,
+         "attn_append_split rejects a short ws");
+  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 2 * 8448 - 1, 1, 65, 2, 64, 320, .125f, nullptr) == -10,
+         "attn_append_split rejects a ws short of the second query tile");
+  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 2 * 8448 - 1, 1, 64, 2, 64, 513, .125f, nullptr) == -10,
+         "attn_append_split rejects a ws short of the second span");
+  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 0, 0, 64, 2, 64, 320, .125f, nullptr) == 0,
+         "attn_append_split B = 0 is a no-op");
+  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, 8448, 1, 64, 2, 128, 320, .125f, nullptr) == -3,
+         "attn_append_split_rows rejects head dim 128");
+  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, big, 1, 64, 2, 64, 32769, .125f, nullptr) == -4,
+         "attn_append_split_rows rejects S_max 32769");
+  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, big, 1, 1025, 2, 64, 320, .125f, nullptr) == -11,
+         "attn_append_split_rows rejects C 1025");
+  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, nullptr, fp, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_append_split_rows rejects a null count");
+  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, nullptr, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_append_split_rows rejects a null ws");
+  EXPECT(jdt_attn_append_split_rows(buf + 4, buf, buf, buf, ip, ip, fp, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
+         "attn_append_split_rows rejects a misaligned qkv");
+  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, big, 65536, 64, 1, 64, 320, .125f, nullptr) == -5,
+         "attn_append_split_rows rejects B * H past the grid");
+  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, 8447, 1, 64, 2, 64, 320, .125f, nullptr) == -10,
+         "attn_append_split_rows rejects a short ws");
+  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, 0, 0, 64, 2, 64, 320, .125f, nullptr) == 0,
+         "attn_append_split_rows B = 0 is a no-op");
   EXPECT(jdt_embed_append(ip, buf, buf, buf, ip, 1, 64, 128, 60, 8, nullptr) == -3, "embed_append rejects d % 8");
   EXPECT(jdt_embed_append(ip, buf, buf, buf, ip, 1, 0, 128, 64, 8, nullptr) == -11, "embed_append rejects C 0");
   EXPECT(jdt_embed_append(ip, buf, buf, buf, ip, 1, 64, 0, 64, 8, nullptr) == -5, "embed_append rejects S_max 0");

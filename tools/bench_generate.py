@@ -3,7 +3,7 @@ default TransformerConfig at B = 1 and B = 16: us per decode step and tokens/s, 
 eagerly against one captured step replayed per token, plus the kernel-launcher calls per step.
 
     python tools/bench_generate.py [--steps 100] [--temperature 0.0] [--ragged] [--seq-len N] [--prompt-len P]
-                                   [--prefill-chunk N[,N...]] [--beams W[,W...]]
+                                   [--prefill-chunk N[,N...]] [--split-append] [--beams W[,W...]]
 
 Each figure: ``--steps`` decode steps after a 16-token prefill, timed with events around the
 whole loop (prefill excluded), median of 5 runs.  ``--seq-len N`` > 128 builds the LM with an
@@ -14,7 +14,9 @@ temperature (``--temperature``, or 0.8 when that is 0): the uniform batch with t
 top-p sampler (k = 50, p = 0.9), and a ragged batch (prompt lengths 1..16, per-row positions)
 with the plain and with the filtered sampler.  ``--prefill-chunk 64,256,1024`` adds, per batch
 size, the time and the peak memory of one prefill of the same prompt through the training forward
-and through chunked prefill at each chunk size (``prefill_lines``).  ``--beams 4,8`` adds, per batch
+and through chunked prefill at each chunk size (``prefill_lines``); with ``--split-append`` each chunk
+line is followed by a ``chunk N split`` line, the same prefill through the split-KV append attention
+of ``Generator(..., split_append=True)``.  ``--beams 4,8`` adds, per batch
 size G (then the number of prompts) and beam count W, the beam step of ``Generator.beam_search`` on G x W
 rows beside the plain sampled step at the same batch and depth (``beam_lines``).
 """
@@ -78,15 +80,20 @@ def timed(run, reset, steps):
     return sorted(ts)[2]
 
 
-def prefill_lines(model, P, B, dev, prompt, chunks, reps=5):
+def prefill_lines(model, P, B, dev, prompt, chunks, reps=5, split_append=False):
     """One line per prefill path -- the training forward, then chunked prefill at each chunk size:
     the time of one ``prefill`` (host clock around a call that ends in a device synchronise,
     median of ``reps`` after a warm-up call that also makes every allocation and GEMM tile
     choice) and the peak of ``torch.cuda.max_memory_allocated`` during the timed calls, beside
-    what was allocated before them (parameters, the KV cache and the path's persistent buffers)."""
+    what was allocated before them (parameters, the KV cache and the path's persistent buffers).
+    ``split_append``: after each ``chunk N`` line a ``chunk N split`` line, the same prefill from a
+    ``Generator(..., split_append=True)`` (the split-KV append attention)."""
     cfg = model.cfg
-    for chunk in [None] + list(chunks):
-        gen = Generator(model, P, B, dev)
+    paths = [(None, False)]
+    for c in chunks:
+        paths += [(c, False)] + ([(c, True)] if split_append else [])
+    for chunk, split in paths:
+        gen = Generator(model, P, B, dev, split_append=split)
         gen.prefill(prompt, chunk=chunk)
         torch.cuda.synchronize(dev)
         held = torch.cuda.memory_allocated(dev)
@@ -100,7 +107,7 @@ def prefill_lines(model, P, B, dev, prompt, chunks, reps=5):
             ts.append((time.perf_counter() - t0) * 1e3)
         peak = torch.cuda.max_memory_allocated(dev)
         ts.sort()
-        path = "training forward" if chunk is None else f"chunk {chunk:4d}"
+        path = "training forward" if chunk is None else f"chunk {chunk:4d}" + (" split" if split else "")
         print(f"prefill  B={B:2d} S={cfg.seq_len} P={prompt.shape[1]} {path:>16}: {ts[len(ts) // 2]:9.2f} ms "
               f"(min {ts[0]:.2f}, max {ts[-1]:.2f}) | {B * prompt.shape[1] / ts[len(ts) // 2] * 1e3:10.0f} tokens/s | "
               f"peak {peak / 2 ** 20:8.1f} MiB ({(peak - held) / 2 ** 20:8.1f} MiB above the {held / 2 ** 20:.1f} MiB "
@@ -170,6 +177,9 @@ def main():
     ap.add_argument("--prefill-chunk", default=None, metavar="N[,N...]",
                     help="extra lines per batch size: the time and peak memory of one prefill through the "
                          "training forward and through chunked prefill at each of these chunk sizes")
+    ap.add_argument("--split-append", action="store_true",
+                    help="with --prefill-chunk: after each chunk line, the same prefill with the split-KV append "
+                         "attention (Generator(split_append=True))")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--ragged", action="store_true", help="extra lines: top-k / top-p and a ragged B = 16 batch")
@@ -207,7 +217,8 @@ def main():
               + ", ".join(f"{k[4:]} x{v}" for k, v in sorted(calls.items())), flush=True)
         if a.prefill_chunk:
             del gen, graph, reset
-            prefill_lines(model, P, B, dev, prompt, [int(v) for v in a.prefill_chunk.split(",")])
+            prefill_lines(model, P, B, dev, prompt, [int(v) for v in a.prefill_chunk.split(",")],
+                          split_append=a.split_append)
         if a.beams:
             beam_lines(model, P, B, dev, [int(v) for v in a.beams.split(",")], a.steps, a.temperature, depth)
     if not a.ragged:
