@@ -10,6 +10,7 @@ one captured decode step replayed per token).
     python generate.py --seq-len 1024 --prompt-len 900 --prefill-chunk 256    # chunked prefill into the cache
     python generate.py --seq-len 4096 --prompt-len 4000 --prefill-chunk 64 --split-append   # split-KV append
     python generate.py --beams 4 --length-penalty 1.0 --eos-id 7              # beam search, 4 hypotheses per prompt
+    python generate.py --train-steps 200 --speculative 4 --draft-layers 1     # speculative decoding, 4 drafts per round
 
 Runs the HIP kernels on a GPU and the torch reference paths on CPU tensors when none is
 present.  The prompt is the first ``--prompt-len`` tokens of ``lm_batch``'s sequences;
@@ -23,7 +24,11 @@ of N prompt rows instead of one pass of the training forward; ``--split-append``
 caches.  ``--beams W`` (1..8) runs a beam search
 instead of sampling: ``--batch`` prompts with W hypotheses each (a generator of batch * W rows), printed
 best first with their scores, ranked by ``log-probability / length ** --length-penalty``.
-Not covered: beams over ragged prompts, diverse or constrained beam search, repetition penalties,
+``--speculative K`` (1..15; not with ``--beams``) decodes speculatively: a draft LM of ``--draft-layers``
+layers (default 1; the same width, vocabulary and ``--seq-len``, trained for the same ``--train-steps`` on
+the same batch) proposes K greedy tokens per round and the target scores them in one append pass; the
+output distribution is the plain decoder's.  The run also prints the rounds and accepted / drafted.
+Not covered: sampled, n-gram or tree drafters, speculative beams, beams over ragged prompts, diverse or constrained beam search, repetition penalties,
 sequences past ``seq_len``, caches longer than 32768 rows or head dims other than 64 on the HIP path,
 multi-GPU or pipeline-split generation.
 """
@@ -67,7 +72,15 @@ def parse_args(argv=None):
                     help="beam search with W hypotheses per prompt (1..8) instead of sampling")
     ap.add_argument("--length-penalty", type=float, default=0.0, metavar="A",
                     help="beam ranking: log-probability / generated length ** A (0: the raw log-probability)")
+    ap.add_argument("--speculative", type=int, default=0, metavar="K",
+                    help="speculative decoding: K greedy drafts per round (1..15) from a small draft LM")
+    ap.add_argument("--draft-layers", type=int, default=1, metavar="L",
+                    help="with --speculative: layers of the draft LM (trained like the target)")
     args = ap.parse_args(argv)
+    if args.speculative and args.beams:
+        ap.error("--speculative and --beams exclude each other: there are no speculative beams")
+    if args.speculative and not 1 <= args.speculative <= 15:
+        ap.error("--speculative K needs K in 1..15")
     if args.split_append and args.prefill_chunk is None:
         ap.error("--split-append needs --prefill-chunk N: only the chunked prefill appends to the cache")
     return args
@@ -109,12 +122,17 @@ def main(args):
 
         restore(tr.state, args.restore)
     data = lm_batch(cfg, global_batch=max(16, args.batch), seed=1)
+    trainers = [tr]
+    if args.speculative:   # the draft: the same LM with fewer layers, trained the same way
+        dcfg = TransformerConfig(seq_len=args.seq_len, n_layers=args.draft_layers)
+        trainers.append(build_lm_pipeline(None, dev, cfg=dcfg, seed=args.model_seed + 1)[0])
     if args.train_steps:
         batch = Batch(data.inputs[:16].to(dev), data.labels[:16].to(dev))
-        for _ in range(args.train_steps):
-            tr.step(batch)
-        if hasattr(tr, "finalize"):
-            tr.finalize()
+        for t in trainers:
+            for _ in range(args.train_steps):
+                t.step(batch)
+            if hasattr(t, "finalize"):
+                t.finalize()
     lens = None
     if args.prompt_lens:
         lens = torch.tensor([int(v) for v in args.prompt_lens.split(",")])
@@ -124,10 +142,13 @@ def main(args):
     prompt = data.inputs[:args.batch, :args.prompt_len].contiguous().to(dev)
     if args.beams:
         return beam_main(args, tr, prompt, dev)
-    gen = Generator(tr.state.apply_fn, tr.state.params, args.batch, dev, split_append=args.split_append)
+    draft = (trainers[1].state.apply_fn, trainers[1].state.params) if args.speculative else None
+    gen = Generator(tr.state.apply_fn, tr.state.params, args.batch, dev, split_append=args.split_append, draft=draft)
     sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
     kw = dict(temperature=args.temperature, seed=args.seed, capture=not args.eager, prompt_lens=lens,
               top_k=args.top_k, top_p=args.top_p, eos_id=args.eos_id, prefill_chunk=args.prefill_chunk)
+    if args.speculative:
+        kw["speculative"] = args.speculative
     out = gen.generate(prompt, args.max_new_tokens, **kw)   # first call: allocations and the step capture
     sync()
     t0 = time.perf_counter()
@@ -142,6 +163,10 @@ def main(args):
           f"new={args.max_new_tokens} temperature={args.temperature} top_k={args.top_k} top_p={args.top_p} "
           f"eos_id={args.eos_id} {'eager' if args.eager or dev.type != 'cuda' else 'captured'}: "
           f"{n / dt:.1f} tokens/s ({dt * 1e3:.2f} ms with the prefill)")
+    if args.speculative:
+        acc, dr = int(gen.spec_accepted.sum()), int(gen.spec_drafted.sum())
+        print(f"[generate] speculative k={args.speculative} draft_layers={args.draft_layers}: {gen.spec_rounds} rounds, "
+              f"{n / max(gen.spec_rounds, 1):.2f} tokens per round over the batch, accepted / drafted = {acc} / {dr}")
 
 
 if __name__ == "__main__":

@@ -58,9 +58,29 @@ candidates by score, then source slot, then rank; then every layer's cache rows 
 ``tokens[:, pos + 1]`` and ``pos`` advances).  The beam state (``BeamState``) lives on the device and
 both launches read ``pos`` there, so the captured beam step replays for every token too.
 
-Out of scope: beams over ragged prompts (per-row positions), diverse or constrained beam search, a
-beam cache that re-routes through an indirection table instead of copying, sharing the prompt's
-cache rows between the beams of a group, repetition penalties, sequences longer than ``seq_len`` (the
+Speculative decoding: ``Generator(..., draft=(draft_model, draft_P))`` and ``generate(..., speculative=k)``
+emit up to k + 1 tokens per verify pass.  The draft is a second ``Generator`` (a full ``TransformerLM`` of
+the same vocabulary and ``seq_len``, any depth or width) whose ``KVCache.tokens`` IS the target's tensor.
+A round (``spec_step(k)``): k greedy per-row draft steps write draft i straight to ``tokens[b, dpos + 1]``;
+``ops.kernels.spec_count`` turns the number drafted into the row's ``count`` = 1 + drafts; one more draft
+step without sampling caches the last draft's row; then ``verify``: ``embed_append`` and
+``append_chunk(count=count, head=True)`` score the C = k + 1 tokens from ``pos`` on in one append slice,
+``ops.kernels.spec_judge`` (csrc/spec.hip, one workgroup per logits row) decides per draft and
+``ops.kernels.spec_commit`` keeps the longest agreed prefix plus one token of the target's own, advances
+``pos_rows`` / ``end`` and sets the drafter's position back to the target's.  Greedy stays greedy and
+sampling stays softmax sampling under the same top-k / top-p filter: the drafts are deterministic, a
+point mass, so "accept d with probability p(d), else redraw from p without d" is the exact rule.  All of
+a round's state (``SpecState``, the per-row cache state) is read on the device, so one captured round
+replays with no host bookkeeping.  Invariant: rejected drafts leave their k / v rows in both caches at
+rows >= ``pos``; those rows are rewritten before they are read, because the next round (or step) appends
+from ``pos``.  ``verify(count)`` is the round without the drafter, for drafts the caller wrote into
+``kv.tokens``: the hook for other drafters.
+
+Out of scope: sampled drafts with a q / p ratio test, n-gram / prompt-lookup or tree drafters (``verify``
+is the hook for them), speculative beams, continuing speculation after ``extend``, a draft with another
+vocabulary, adapting k per row or per round, beams over ragged prompts (per-row positions), diverse or
+constrained beam search, a beam cache that re-routes through an indirection table instead of copying,
+sharing the prompt's cache rows between the beams of a group, repetition penalties, sequences longer than ``seq_len`` (the
 learned positions end there), multi-GPU or pipeline-split generation, paged or compacted
 caches, ``generate()`` continuing a live cache, split append as the default, a span size chosen
 per shape (the spans are absolute so that the cut does not change the bits), removing finished
@@ -150,14 +170,38 @@ class BeamState:
             t.zero_()
 
 
+class SpecState:
+    """The device state of speculative rounds of ``k`` drafts over ``batch`` rows: ``count`` (tokens a row
+    appends this round: 1 + its drafts; 0: the row sits the round out), ``n_drafted``, the judge's
+    scratch ``acc`` / ``repl`` int32 [B, k + 1], and the counters ``drafted`` / ``accepted`` / ``emitted``
+    (sums over the rounds since ``reset``) and ``last_accept`` (drafts kept in the row's last round)."""
+
+    def __init__(self, batch: int, k: int, device):
+        self.k, self.C = k, k + 1
+        i32 = lambda *shape: torch.zeros(*shape, dtype=torch.int32, device=device)  # noqa: E731
+        self.count, self.n_drafted = i32(batch), i32(batch)
+        self.acc, self.repl = i32(batch, self.C), i32(batch, self.C)
+        self.drafted, self.accepted, self.emitted, self.last_accept = i32(batch), i32(batch), i32(batch), i32(batch)
+
+    def reset(self):
+        for t in (self.drafted, self.accepted, self.emitted, self.last_accept):
+            t.zero_()
+
+
+SPEC_CHECK_ROUNDS = 4   # speculative generate reads "every row finished" on the host this often (untuned)
+
+
 class Generator:
     """Generation with a full (un-split) ``TransformerLM`` and its parameters ``P`` for a
     fixed batch of ``batch`` sequences on ``device``.  ``split_append`` (opt-in): everything that
     appends to the cache -- ``prefill(chunk=)``, ``extend``, ``generate(prefill_chunk=)``,
     ``beam_search(prefill_chunk=)`` -- runs the split-KV append attention (``KVCache.append_ws``
-    holds its partials) instead of the one-launch kernel."""
+    holds its partials) instead of the one-launch kernel.  ``draft`` = (draft_model, draft_P): the
+    drafter of speculative decoding, a full ``TransformerLM`` of the same ``vocab_size`` and
+    ``seq_len`` (``self.draft`` is its ``Generator``; its ``kv.tokens`` is this one's tensor)."""
 
-    def __init__(self, model: TransformerLM, P: FlatParams, batch: int, device, split_append: bool = False):
+    def __init__(self, model: TransformerLM, P: FlatParams, batch: int, device, split_append: bool = False,
+                 draft=None):
         if not (model.has_embed and model.has_head and list(model.layers) == list(range(model.cfg.n_layers))):
             raise ValueError("Generator needs the full model (embedding, every layer and the head): "
                              "pipeline-split stages cannot generate")
@@ -181,6 +225,21 @@ class Generator:
         self.beam_scores: Optional[torch.Tensor] = None    # fp32 [G, W]: the last beam_search's ranking scores
         self.beam_logprobs: Optional[torch.Tensor] = None  # fp32 [G, W]: its raw log-probability sums
         self.beam_steps = 0                          # steps the last beam_search ran
+        self.draft: Optional[Generator] = None       # the drafter (speculative decoding)
+        self._draft_sync = False                     # the draft's cache and position follow the target's
+        self._spec_states: dict = {}                 # k -> SpecState (kept: a captured round holds its pointers)
+        self.spec_rounds = 0                         # rounds the last speculative generate ran
+        self.spec_drafted: Optional[torch.Tensor] = None    # int32 [B]: drafts it proposed per row,
+        self.spec_accepted: Optional[torch.Tensor] = None   # ... drafts kept
+        self.spec_emitted: Optional[torch.Tensor] = None    # ... and tokens emitted
+        if draft is not None:
+            dm, dP = draft
+            dc = getattr(dm, "cfg", None)
+            if not isinstance(dm, TransformerLM) or (dc.vocab_size, dc.seq_len) != (model.cfg.vocab_size,
+                                                                                   model.cfg.seq_len):
+                raise ValueError("the draft must be a TransformerLM with the target's vocab_size and seq_len")
+            self.draft = Generator(dm, dP, self.batch, self.device, split_append=split_append)
+            self.draft.kv.tokens = self.kv.tokens    # one tensor: the drafts land where the verify pass reads them
 
     # ------------------------------------------------------------------ prefill
     def prefill(self, prompt: torch.Tensor, prompt_lens: Optional[torch.Tensor] = None, *,
@@ -221,6 +280,7 @@ class Generator:
         kv.tokens.zero_()
         kv.tokens[:, :Pn] = prompt
         self._live = True
+        self._draft_sync = False
         if chunk is not None:
             self.prefill_rows = 0
             kv.per_row = lens is not None
@@ -288,6 +348,7 @@ class Generator:
             need = K.attention_append_ws_floats(B, c.n_heads, min(chunk, max(nb)), c.seq_len)
             if kv.append_ws is None or kv.append_ws.numel() < need:
                 kv.append_ws = torch.empty(need, dtype=torch.float32, device=self.device)
+                self._drop_spec_graphs()
         for lo in range(0, max(nb), chunk):
             C = min(chunk, max(nb) - lo)
             cnt = [min(max(v - lo, 0), C) for v in nb]
@@ -353,6 +414,7 @@ class Generator:
             kv.tokens[b, p + 1:p + 1 + v] = tokens[b, :v]
         if kv.per_row:
             kv.end.fill_(c.seq_len)
+        self._draft_sync = False   # the target moves on without the draft
         return self.advance(torch.tensor(nb) if kv.per_row else n, chunk=chunk, logits=logits)
 
     # ------------------------------------------------------------------ one step
@@ -364,6 +426,7 @@ class Generator:
         ``pos`` is ``kv.pos_rows``, and a row at its ``end`` neither samples nor advances."""
         kv, P = self.kv, self.P
         pos = kv.live_pos
+        self._draft_sync = False   # a plain step moves the target without its draft
         K.embed_decode(kv.tokens, P.s("embed/wte"), P.s("embed/wpe"), pos, out=self.x)
         self.logits = self.model.decode_step(P, kv, self.x)
         if not sample:
@@ -404,11 +467,139 @@ class Generator:
         g.replay()
         self.logits = logits
 
+    # ------------------------------------------------------------------ speculative decoding
+    def _spec_state(self, k: int) -> SpecState:
+        """The checks common to ``spec_step`` / ``verify`` and the state of rounds of ``k`` drafts (made
+        on first use, with the round's workspaces, so that nothing is allocated under a capture)."""
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= K.SPEC_MAX_DRAFTS:
+            raise ValueError(f"speculative k must be an int in 1..{K.SPEC_MAX_DRAFTS}, got {k!r}")
+        if not self._live:
+            raise ValueError("speculative decoding needs a live cache: call prefill (or generate) first")
+        if not self.kv.per_row:
+            raise ValueError("speculative decoding needs the per-row cache state (prefill with prompt_lens)")
+        st = self._spec_states.get(k)
+        if st is None:
+            st = self._spec_states[k] = SpecState(self.batch, k, self.device)
+        c, C = self.model.cfg, k + 1
+        if C not in self._chunk_bufs:
+            self._chunk_bufs[C] = torch.zeros(self.batch * C, c.d_model, dtype=torch.bfloat16, device=self.device)
+        if self.split_append:
+            need = K.attention_append_ws_floats(self.batch, c.n_heads, C, c.seq_len)
+            if self.kv.append_ws is None or self.kv.append_ws.numel() < need:
+                self.kv.append_ws = torch.empty(need, dtype=torch.float32, device=self.device)
+                self._drop_spec_graphs()
+        return st
+
+    def _drop_spec_graphs(self):
+        """A captured round holds ``kv.append_ws``' pointer: a replaced buffer retires those graphs."""
+        for gen in (self, self.draft):
+            if gen is not None:
+                gen._graphs = {key: v for key, v in gen._graphs.items() if key[0] != "spec"}
+
+    def _verify(self, st: SpecState, dpos=None, dend=None) -> torch.Tensor:
+        kv, P = self.kv, self.P
+        x = self._chunk_bufs[st.C]
+        K.embed_append(kv.tokens, P.s("embed/wte"), P.s("embed/wpe"), kv.pos_rows, st.C, count=st.count, out=x)
+        self.logits = self.model.append_chunk(P, kv, x, st.C, count=st.count, head=True)
+        K.spec_judge(self.logits, kv.tokens, kv.pos_rows, kv.end, st.count, st.acc, st.repl,
+                     temperature=self.temperature, seed=self.seed, top_k=self.top_k, top_p=self.top_p)
+        K.spec_commit(st.acc, st.repl, kv.tokens, kv.pos_rows, kv.end, st.count, st.drafted, st.accepted, st.emitted,
+                      st.last_accept, eos_id=self.eos_id, dpos=dpos, dend=dend)
+        return self.logits
+
+    def verify(self, count: torch.Tensor, k: Optional[int] = None) -> torch.Tensor:
+        """A speculative round without the drafter.  Row b's ``count[b] - 1`` drafts are already in
+        ``kv.tokens[b, pos + 1 ..]``; ``count`` (int [B], each 0 or 1..k + 1) is copied into the round's
+        state and the C = k + 1 tokens from ``pos`` on go through ``embed_append``, ``append_chunk(count=,
+        head=True)``, ``spec_judge`` and ``spec_commit`` (temperature / seed / top_k / top_p / eos_id: the
+        attributes of that name).  A row whose count would pass ``end`` or the cache sits the round out
+        (see ``ops.kernels.spec_judge``).  ``k`` defaults to ``max(count) - 1`` (read on the host).  Returns
+        the round's logits [B * C, vocab]: row b * C + i predicts token index pos_before + i + 1.
+        ``self.spec_state(k)`` holds ``acc`` / ``repl`` / ``last_accept`` and the counters.  The draft
+        generator, if any, is not told: ``spec_step`` refuses to go on after a ``verify``."""
+        count = torch.as_tensor(count)
+        if count.shape != (self.batch,) or count.dtype.is_floating_point:
+            raise ValueError(f"count must be {self.batch} integers, got {tuple(count.shape)} {count.dtype}")
+        if k is None:
+            k = max(int(count.max()) - 1, 1)
+        st = self._spec_state(k)
+        st.count.copy_(count.to(device=self.device, dtype=torch.int32))
+        self._draft_sync = False
+        return self._verify(st)
+
+    def spec_state(self, k: int) -> SpecState:
+        """The ``SpecState`` of rounds of ``k`` drafts (``verify`` / ``spec_step`` create it)."""
+        return self._spec_states[k]
+
+    def spec_step(self, k: int) -> torch.Tensor:
+        """One speculative round of up to ``k`` drafts per row (eager or under a capture; needs ``draft``
+        in sync with the target: a speculative ``generate`` brings it there, ``extend`` / ``prefill`` /
+        ``verify`` / ``step`` take it away).  k greedy per-row draft steps bounded by the draft's ``end`` (a draft
+        equal to ``eos_id`` ends a row's drafting), ``spec_count``, one more draft step without sampling
+        (the draft cache then holds the row of the last draft too), then the verify pass, whose commit
+        sets the draft's position and end back to the target's.  Returns the verify logits
+        [B * (k + 1), vocab]."""
+        if self.draft is None:
+            raise ValueError("spec_step needs a draft model: Generator(..., draft=(model, P))")
+        st = self._spec_state(k)
+        if not self._draft_sync:
+            raise ValueError("the draft is not in sync with the target (extend / prefill / verify / step moved the target "
+                             "alone): start again with generate(..., speculative=k)")
+        d, kv = self.draft, self.kv
+        d.temperature, d.eos_id = 0.0, self.eos_id
+        for _ in range(k):
+            d.step()
+        torch.sub(d.kv.pos_rows, kv.pos_rows, out=st.n_drafted)
+        K.spec_count(kv.pos_rows, kv.end, st.n_drafted, k, self.model.cfg.seq_len, out=st.count)
+        d.step(sample=False)
+        return self._verify(st, d.kv.pos_rows, d.kv.end)
+
+    def _generate_spec(self, prompt, max_new_tokens, k, graph, prompt_lens, pad_id, prefill_chunk):
+        c, kv, d = self.model.cfg, self.kv, self.draft
+        if d is None:
+            raise ValueError("speculative decoding needs a draft model: Generator(..., draft=(model, P))")
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= K.SPEC_MAX_DRAFTS:
+            raise ValueError(f"speculative must be an int in 1..{K.SPEC_MAX_DRAFTS}, got {k!r}")
+        Pn = prompt.shape[1] if prompt.dim() == 2 else 0
+        if prompt_lens is None:
+            prompt_lens = torch.full((self.batch,), Pn, dtype=torch.int32)
+        lens = torch.as_tensor(prompt_lens)
+        longest = int(lens.max()) if lens.numel() else 0
+        if max_new_tokens < 0 or longest + max_new_tokens > c.seq_len:
+            raise ValueError(f"longest prompt {longest} + max_new_tokens {max_new_tokens} exceeds seq_len "
+                             f"{c.seq_len} (the learned positions end there)")
+        self.prefill(prompt, lens, chunk=prefill_chunk)
+        d.prefill(prompt, lens, chunk=prefill_chunk)   # the same tokens into the shared tensor again
+        kv.end.copy_(kv.pos_rows + 1 + max_new_tokens)
+        d.kv.pos_rows.copy_(kv.pos_rows)
+        d.kv.end.copy_((kv.end.clamp(max=c.seq_len) - 1).clamp(min=0))
+        st = self._spec_state(k)
+        st.reset()
+        self._draft_sync = True
+        step = lambda: self.spec_step(k)  # noqa: E731
+        key = ("spec", k, self.temperature, self.seed, self.top_k, self.top_p, self.eos_id)
+        self.spec_rounds = 0
+        for r in range(1, max_new_tokens + 1):   # every round emits a token per unfinished row
+            if graph:
+                self._replay(step, key)
+            else:
+                step()
+            self.spec_rounds = r
+            # a host read serialises the replay loop: look only every SPEC_CHECK_ROUNDS rounds
+            if r % SPEC_CHECK_ROUNDS == 0 and r < max_new_tokens and bool((kv.pos_rows + 1 >= kv.end).all()):
+                break
+        self.spec_drafted, self.spec_accepted, self.spec_emitted = (t.clone() for t in (st.drafted, st.accepted,
+                                                                                         st.emitted))
+        self.lengths = kv.pos_rows + 1
+        out = kv.tokens[:, :longest + max_new_tokens].clone()
+        out[torch.arange(out.shape[1], device=self.device)[None] >= self.lengths[:, None]] = pad_id
+        return out
+
     # ------------------------------------------------------------------ generate
     def generate(self, prompt: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, seed: int = 0,
                  capture: bool = True, *, prompt_lens: Optional[torch.Tensor] = None, top_k: int = 0,
                  top_p: float = 1.0, eos_id: Optional[int] = None, pad_id: int = 0,
-                 prefill_chunk: Optional[int] = None) -> torch.Tensor:
+                 prefill_chunk: Optional[int] = None, speculative: Optional[int] = None) -> torch.Tensor:
         """``prompt`` int [B, P] -> int32 [B, P + max_new_tokens] (the prompt, then the new
         tokens).  ``temperature == 0``: greedy; otherwise softmax(logits / T) sampling from
         Philox stream ``seed``, restricted to the ``top_k`` largest logits (0: off) and, of
@@ -422,7 +613,15 @@ class Generator:
         max_new_tokens; a row that emits ``eos_id`` stops there (the EOS is its last token)
         while the others go on, and the loop ends early once every row has finished (checked
         every 16 steps).  Returns int32 [B, max(len) + max_new_tokens] with ``pad_id`` at and
-        past each row's final length; ``self.lengths`` (int32 [B]) holds those lengths."""
+        past each row's final length; ``self.lengths`` (int32 [B]) holds those lengths.
+
+        ``speculative`` = k in 1..15 (needs ``draft``): speculative rounds of up to k greedy drafts per
+        row (``spec_step``) instead of decode steps; always the per-row mode and its ragged return
+        format, the output distribution is the plain one's.  Both models are prefilled
+        (``prefill_chunk`` for both), ``capture`` captures one round per (k, sampler setting), the loop
+        ends once every row has finished (read every ``SPEC_CHECK_ROUNDS`` rounds, an untuned constant)
+        and after at most ``max_new_tokens`` rounds.  Sets ``spec_rounds`` and ``spec_drafted`` /
+        ``spec_accepted`` / ``spec_emitted`` (int32 [B])."""
         c = self.model.cfg
         Pn = prompt.shape[1] if prompt.dim() == 2 else 0
         if top_k < 0 or not 0.0 < top_p <= 1.0:
@@ -432,6 +631,10 @@ class Generator:
         self.eos_id = -1 if eos_id is None else int(eos_id)
         graph = capture and self.device.type == "cuda"
         run = self._replay if graph else self.step
+        if speculative is not None:
+            if self.eos_id >= c.vocab_size or (eos_id is not None and self.eos_id < 0):
+                raise ValueError(f"eos_id {eos_id} outside [0, {c.vocab_size})")
+            return self._generate_spec(prompt, max_new_tokens, speculative, graph, prompt_lens, pad_id, prefill_chunk)
         if prompt_lens is None and eos_id is None:
             if max_new_tokens < 0 or Pn + max_new_tokens > c.seq_len:
                 raise ValueError(f"prompt length {Pn} + max_new_tokens {max_new_tokens} exceeds seq_len "

@@ -165,6 +165,16 @@ _SIGS = {
     "jdt_beam_reorder": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                  c_int, c_void_p]),
+    # csrc/spec.hip: (pos, end, n_drafted, count, B, k, S_max, stream)
+    "jdt_spec_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    # (logits, ld, B, C, V, temperature, seed, stream_id, tokens, S_max, pos, end, count, acc, repl, top_k, top_p,
+    #  stream)
+    "jdt_spec_judge": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_float, c_ulonglong, ctypes.c_uint, c_void_p,
+                               c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p]),
+    # (acc, repl, B, C, tokens, S_max, pos, end, count, eos_id, drafted, accepted, emitted, last_accept, dpos, dend,
+    #  stream)
+    "jdt_spec_commit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -25,7 +25,8 @@
 // embed_decode: x[b] = wte[tokens[b, pos]] + wpe[pos]   (the bits embed_fwd_kernel stores)
 // embed_append: the same for a block of C tokens per sequence from pos on (attn_append.hip's input)
 // sample:       argmax (temperature 0) or inverse-CDF sampling of softmax(logits / T),
-//               optionally restricted to the top-k / top-p set (FILT = true)
+//               optionally restricted to the top-k / top-p set (FILT = true); the argmax, the
+//               threshold and the draw are row_select.h's, shared with the speculative judge
 #include "common.h"
 #include "row_select.h"
 
@@ -257,80 +258,6 @@ __global__ void __launch_bounds__(256) embed_append_kernel(const int* __restrict
   *reinterpret_cast<u32x4*>(out + (long)row * d + c) = bf16x8_add(a, e);
 }
 
-// the sampling weight of a logit; FILT: 0 below the threshold key
-template <bool FILT>
-__device__ __forceinline__ float weight(float x, float gmx, float inv_t, unsigned thr) {
-  if (FILT && key16(x) < thr) return 0.f;
-  return __expf((x - gmx) * inv_t);
-}
-
-// The threshold key max(key_k, key_p) of a row (every thread of the workgroup calls it and
-// gets the same value).  top-k: bf16 has 65,536 values, so two 256-bin histograms of integer
-// counts (high byte of the key, then the low byte inside the selected bin) give the key of
-// the k-th largest logit exactly.  top-p: a binary search over the key in [key_k, key(max)];
-// each probe sums the weights at or above the key in a fixed order (the thread's chunk in
-// column order, the wave, the four waves), so a row always gives the same threshold.
-__device__ __forceinline__ unsigned filter_threshold(const bf16_t* row, int V, int vec, int beg, int end, float gmx,
-                                                     float inv_t, int top_k, float top_p) {
-  __shared__ int s_hist[256], s_scan[4], s_sel[2];
-  __shared__ float s_mass[2][4];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  unsigned key_k = 0;
-  if (top_k > 0 && top_k < V) {
-    int want = top_k;   // rank still to go, counted from the top of the current bin range
-    unsigned hi_bin = 0;
-    for (int level = 0; level < 2; ++level) {
-      s_hist[tid] = 0;
-      __syncthreads();
-      for (int i0 = beg; i0 < end; i0 += 8) {
-        float x[8];
-        logits8(row, i0, V, vec, x);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const unsigned key = key16(x[e]);
-          if (i0 + e < V && (level == 0 || (key >> 8) == hi_bin))
-            atomicAdd(&s_hist[level == 0 ? key >> 8 : key & 255u], 1);   // integer counts: order-free
-        }
-      }
-      __syncthreads();
-      const int bin = 255 - tid, h = s_hist[bin];   // descending: thread 0 has the top bin
-      const int inc = block_scan_incl(h, s_scan);
-      if (inc >= want && inc - h < want) {   // exactly one thread: the counts sum to >= want
-        s_sel[0] = bin;
-        s_sel[1] = want - (inc - h);
-      }
-      __syncthreads();
-      if (level == 0) hi_bin = (unsigned)s_sel[0];
-      else key_k = (hi_bin << 8) | (unsigned)s_sel[0];
-      want = s_sel[1];
-    }
-  }
-  if (!(top_p < 1.f)) return key_k;
-  int probe = 0;
-  auto mass = [&](unsigned thr) {
-    float m = 0.f;
-    for (int i0 = beg; i0 < end; i0 += 8) {
-      float x[8];
-      logits8(row, i0, V, vec, x);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) m += weight<true>(x[e], gmx, inv_t, thr);
-    }
-    m = wave_sum_dpp(m);
-    float* s = s_mass[probe++ & 1];   // two buffers: one barrier per probe
-    if (lane == 0) s[w] = m;
-    __syncthreads();
-    return (s[0] + s[1]) + (s[2] + s[3]);
-  };
-  const float target = top_p * mass(key_k);   // <= the top-k mass, so key_k always qualifies
-  unsigned lo = key_k, hi = max(key16(gmx), key_k);
-  while (lo < hi) {   // uniform: every thread sees the same masses
-    const unsigned mid = (lo + hi + 1) >> 1;
-    if (mass(mid) >= target) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 // One workgroup per row; thread t owns the contiguous columns [t * per, (t + 1) * per).
 // temperature == 0: argmax, lowest index on ties.  Otherwise inverse-CDF sampling: weights
 // w_i = exp((x_i - max) / T) in fp32, a fixed-order prefix sum over the threads' chunk sums,
@@ -354,9 +281,7 @@ __global__ void __launch_bounds__(256) sample_kernel(const bf16_t* __restrict__ 
                                                     int* __restrict__ tokens, int S_max, int* pos_ptr,
                                                     unsigned* ticket, int vec, int* end_ptr, int eos_id, int top_k,
                                                     float top_p) {
-  __shared__ float s_mx[4], s_w[4];
-  __shared__ int s_am[4], s_own[4];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, b = blockIdx.x;
+  const int tid = threadIdx.x, b = blockIdx.x;
   const int pos = pos_ptr[ROWS ? b : 0];
   if (ROWS) {
     if (pos < 0 || pos + 1 >= min(end_ptr[b], S_max)) return;   // finished or full: uniform over the workgroup
@@ -375,79 +300,17 @@ __global__ void __launch_bounds__(256) sample_kernel(const bf16_t* __restrict__ 
   const bf16_t* row = logits + (long)b * ld;
   const int per = (((V + 255) / 256) + 7) & ~7;
   const int beg = tid * per, end = min(beg + per, V);
-  float mx = -INFINITY;
-  int am = INT_MAX;
-  for (int i0 = beg; i0 < end; i0 += 8) {
-    float x[8];
-    logits8(row, i0, V, vec, x);
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (x[e] > mx) { mx = x[e]; am = i0 + e; }
-  }
-  const float wmx = wave_max_dpp(mx);
-  const int wam = wave_min_dpp(mx == wmx ? am : INT_MAX);
-  if (lane == 0) { s_mx[w] = wmx; s_am[w] = wam; }
-  __syncthreads();
-  const float gmx = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
-  int gam = INT_MAX;
-#pragma unroll
-  for (int k = 0; k < 4; ++k)
-    if (s_mx[k] == gmx) gam = min(gam, s_am[k]);
-  if (gam >= V) gam = 0;   // a row with no finite maximum
+  float gmx;
+  const int gam = row_argmax(row, V, vec, beg, end, gmx);
   if (temperature <= 0.f) {
     if (tid == 0) emit(gam);
   } else {
     const float inv_t = 1.f / temperature;
     unsigned thr = 0;   // FILT: columns whose key is below it weigh 0
     if (FILT) thr = filter_threshold(row, V, vec, beg, end, gmx, inv_t, top_k, top_p);
-    float tsum = 0.f;
-    for (int i0 = beg; i0 < end; i0 += 8) {
-      float x[8];
-      logits8(row, i0, V, vec, x);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) tsum += weight<FILT>(x[e], gmx, inv_t, thr);
-    }
-    float inc = tsum;   // inclusive scan over the wave's threads
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-      const float t = __shfl_up(inc, o, WAVE);
-      if (lane >= o) inc += t;
-    }
-    const float prev = __shfl_up(inc, 1, WAVE);
-    if (lane == WAVE - 1) s_w[w] = inc;
-    __syncthreads();
-    float woff = 0.f, total = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (k == w) woff = total;
-      total += s_w[k];
-    }
     const u32x4 r = philox4x32(seed, (uint64_t)b, ((uint64_t)(unsigned)pos << 32) | (uint64_t)stream_id);
-    const float target = (float)(r.x >> 8) * (1.0f / 16777216.0f) * total;
-    const int own = wave_min_dpp(woff + inc > target ? tid : INT_MAX);
-    if (lane == 0) s_own[w] = own;
-    __syncthreads();
-    const int owner = min(min(s_own[0], s_own[1]), min(s_own[2], s_own[3]));
-    if (owner == INT_MAX) {   // u * total rounded up to total
-      if (tid == 0) emit(gam);
-    } else if (tid == owner) {
-      float run = woff + (lane > 0 ? prev : 0.f);
-      int pick = -1, last = -1;
-      for (int i0 = beg; i0 < end && pick < 0; i0 += 8) {
-        float x[8];
-        logits8(row, i0, V, vec, x);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float wt = weight<FILT>(x[e], gmx, inv_t, thr);
-          run += wt;
-          if (wt > 0.f && pick < 0) {
-            last = i0 + e;
-            if (run > target) pick = i0 + e;
-          }
-        }
-      }
-      emit(pick >= 0 ? pick : (last >= 0 ? last : gam));
-    }
+    const int tok = row_draw<FILT, false>(row, V, vec, beg, end, gmx, gam, inv_t, thr, r.x, -1);
+    if (tok >= 0) emit(tok);   // one thread
   }
   if (ROWS) return;
   __syncthreads();

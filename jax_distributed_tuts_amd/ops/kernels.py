@@ -1389,8 +1389,169 @@ def sample_tokens(logits: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor,
     return tokens
 
 
+# ----------------------------------------------------------------------------- speculative decoding (csrc/spec.hip)
+SPEC_MAX_DRAFTS = 15   # drafts per row and round; a round scores C = k + 1 <= 16 tokens per row (SP_MAXC)
+
+
+def _spec_live(pos, end, count, C: int, S_max: int) -> torch.Tensor:
+    """The rows that take part in a round: 0 <= p, 1 <= count <= C and p + count < min(end, S_max)."""
+    p, n = pos.long(), count.long()
+    return (p >= 0) & (n >= 1) & (n <= C) & (p + n < end.long().clamp(max=S_max))
+
+
+def spec_count(pos: torch.Tensor, end: torch.Tensor, n_drafted: torch.Tensor, k: int, S_max: int,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The tokens each row appends in a speculative round, ``count`` int32[B]: 0 for a row with
+    ``p < 0`` or ``p + 1 >= lim`` (p = pos[b], lim = min(end[b], S_max)), else ``1 + min(n_drafted[b],
+    k, lim - p - 2)`` (a negative ``n_drafted`` counts as 0).  The append then never passes the end
+    of the cache and the last token the round can emit, index p + count, stays below lim.  One
+    launch, no host read."""
+    B = pos.numel()
+    if not 1 <= int(k) <= SPEC_MAX_DRAFTS:
+        raise ValueError(f"k must be in 1..{SPEC_MAX_DRAFTS}, got {k}")
+    for t in (pos, end, n_drafted):
+        assert t.dtype == torch.int32 and t.numel() == B
+    if out is None:
+        out = torch.zeros(B, dtype=torch.int32, device=pos.device)
+    assert out.dtype == torch.int32 and out.numel() == B
+    if not _is_gpu(pos):
+        p, lim = pos.long(), end.long().clamp(max=S_max)
+        c = 1 + torch.minimum(n_drafted.long().clamp(max=int(k)), lim - p - 2).clamp(min=0)
+        out.copy_(torch.where((p >= 0) & (p + 1 < lim), c, torch.zeros_like(c)).to(torch.int32))
+        return out
+    rc = _lib.lib().jdt_spec_count(_ptr(pos), _ptr(end), _ptr(n_drafted), _ptr(out), B, int(k), int(S_max),
+                                   _lib.stream_ptr())
+    _lib.check(rc, "jdt_spec_count")
+    return out
+
+
+def spec_judge(logits: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor, end: torch.Tensor,
+               count: torch.Tensor, acc: torch.Tensor, repl: torch.Tensor, *, temperature: float = 0.0,
+               seed: int = 0, stream_id: int = 0, top_k: int = 0, top_p: float = 1.0):
+    """Judge the drafts of a speculative round.  ``logits`` [B*C, V] bf16: row b*C + i is the target's
+    prediction after token index p + i (p = pos[b]); row b's n = count[b] - 1 drafts are
+    ``tokens[b, p + 1 .. p + n]``; ``acc`` / ``repl`` int32 [B, C].  For i < count[b]:
+
+    ``temperature == 0``: g = argmax (lowest index on ties), ``acc[b, i] = (i < n and draft == g)``,
+    ``repl[b, i] = g``.  Otherwise, with the weights ``sample_tokens`` uses (exp((x - max) / T), zero
+    outside the top-k / top-p set of ``_filter_weights``), W their sum and u0, u1 = words 0, 1 of
+    philox4x32(seed, counter = b, offset = ((p + i) << 32) | stream_id): for i < n, ``acc = (0 <= d < V
+    and u1 * W < w_d)`` and ``repl`` = the inverse-CDF draw with u0 over the weights with w_d zeroed
+    (nothing left: the argmax); for i == n, ``acc = 0`` and ``repl`` = the plain draw with u0: the token
+    ``sample_tokens`` writes for that row, position, seed and filter.
+
+    A row with ``p < 0``, ``count`` outside 1..C or ``p + count >= min(end, S_max)`` is left alone, as
+    are the entries i >= count[b]."""
+    B, S_max = tokens.shape
+    C, V = acc.shape[1], logits.shape[1]
+    if not 1 <= C <= SPEC_MAX_DRAFTS + 1:
+        raise ValueError(f"C must be in 1..{SPEC_MAX_DRAFTS + 1}, got {C}")
+    if top_k < 0 or not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_k must be >= 0 and top_p in (0, 1], got top_k={top_k} top_p={top_p}")
+    assert temperature >= 0.0 and 0 <= stream_id < 2 ** 32
+    assert logits.shape[0] == B * C and acc.shape == repl.shape == (B, C)
+    for t in (tokens, pos, end, count, acc, repl):
+        assert t.dtype == torch.int32
+    assert pos.numel() == end.numel() == count.numel() == B
+    seed = int(seed) & (2 ** 64 - 1)
+    if not _is_gpu(logits):
+        live = _spec_live(pos, end, count, C, S_max)
+        b_i = [(b, i) for b in live.nonzero()[:, 0].tolist() for i in range(int(count[b]))]
+        if not b_i:
+            return
+        bs, js = (torch.tensor(v) for v in zip(*b_i))
+        pl, n = pos.long()[bs], count.long()[bs] - 1
+        has = js < n
+        d = torch.where(has, tokens[bs, (pl + 1 + js).clamp(max=S_max - 1)].long(), torch.full_like(js, -1))
+        x = _bf(logits.float())[bs * C + js]
+        g = x.argmax(-1)
+        if temperature <= 0.0:
+            acc[bs, js] = (has & (d == g)).to(torch.int32)
+            repl[bs, js] = g.to(torch.int32)
+            return
+        w = torch.exp((x - x.max(-1, keepdim=True).values) / float(temperature))
+        if 0 < top_k < V or top_p < 1.0:
+            w = _filter_weights(x, w, int(top_k), float(top_p))
+        u = torch.empty(2, len(b_i), dtype=torch.float32)
+        at = pl + js
+        for p in at.unique().tolist():   # one Philox offset per distinct position
+            sel = at == p
+            for word in (0, 1):
+                u[word, sel] = torch.from_numpy(philox_uniform(seed, (p << 32) | int(stream_id), bs[sel].numpy(),
+                                                               word)).float()
+        in_v = has & (d >= 0) & (d < V)
+        dc = d.clamp(0, V - 1)[:, None]
+        wd = torch.where(in_v, w.gather(1, dc)[:, 0], torch.zeros(len(b_i)))
+        ok = in_v & (u[1] * w.sum(-1) < wd)
+        w2 = w.scatter(1, dc, torch.where(in_v, torch.zeros(len(b_i)), w.gather(1, dc)[:, 0])[:, None])
+        cum = torch.cumsum(w2, -1)
+        hit = cum > (u[0] * cum[:, -1])[:, None]
+        acc[bs, js] = ok.to(torch.int32)
+        repl[bs, js] = torch.where(hit.any(-1), hit.to(torch.uint8).argmax(-1), g).to(torch.int32)
+        return
+    assert logits.dtype == torch.bfloat16 and logits.stride(1) == 1
+    for t in (tokens, acc, repl):
+        assert t.is_contiguous()
+    rc = _lib.lib().jdt_spec_judge(_ptr(logits), logits.stride(0), B, C, V, float(temperature), seed, int(stream_id),
+                                   _ptr(tokens), S_max, _ptr(pos), _ptr(end), _ptr(count), _ptr(acc), _ptr(repl),
+                                   int(top_k), float(top_p), _lib.stream_ptr())
+    _lib.check(rc, "jdt_spec_judge")
+
+
+def spec_commit(acc: torch.Tensor, repl: torch.Tensor, tokens: torch.Tensor, pos: torch.Tensor, end: torch.Tensor,
+                count: torch.Tensor, drafted: torch.Tensor, accepted: torch.Tensor, emitted: torch.Tensor,
+                last_accept: torch.Tensor, *, eos_id: int = -1, dpos: Optional[torch.Tensor] = None,
+                dend: Optional[torch.Tensor] = None):
+    """Commit a judged round, per row (the rows ``spec_judge`` left alone are left alone).  a = the
+    first i with ``acc[b, i] == 0`` (at the latest i = n = count[b] - 1).  If ``eos_id >= 0`` and an
+    accepted draft d_j = tokens[b, p + j] (smallest j in 1..a) equals it: ``pos[b] = p + j``, ``end[b] =
+    p + j + 1``, j tokens emitted and j drafts kept.  Otherwise ``tokens[b, p + a + 1] = repl[b, a]``,
+    ``pos[b] = p + a + 1`` (a + 1 tokens emitted, a drafts kept) and ``end[b] = p + a + 2`` if that token
+    is ``eos_id``.  ``drafted += n``, ``accepted +=`` the drafts kept, ``emitted +=`` the tokens emitted,
+    ``last_accept =`` the drafts kept.  ``dpos`` / ``dend`` (the drafter's per-row state, both or
+    neither): for every row, ``dpos[b] = pos[b]`` and ``dend[b] = max(min(end[b], S_max) - 1, 0)`` from
+    the state after the round."""
+    B, S_max = tokens.shape
+    C = acc.shape[1]
+    if not 1 <= C <= SPEC_MAX_DRAFTS + 1:
+        raise ValueError(f"C must be in 1..{SPEC_MAX_DRAFTS + 1}, got {C}")
+    assert (dpos is None) == (dend is None) and acc.shape == repl.shape == (B, C)
+    for t in (acc, repl, tokens, pos, end, count, drafted, accepted, emitted, last_accept, dpos, dend):
+        assert t is None or t.dtype == torch.int32
+    for t in (pos, end, count, drafted, accepted, emitted, last_accept, dpos, dend):
+        assert t is None or t.numel() == B
+    if not _is_gpu(tokens):
+        live = _spec_live(pos, end, count, C, S_max)
+        for b in live.nonzero()[:, 0].tolist():
+            p, n = int(pos[b]), int(count[b]) - 1
+            a = next((i for i in range(n) if int(acc[b, i]) == 0), n)
+            j = next((j for j in range(1, a + 1) if eos_id >= 0 and int(tokens[b, p + j]) == eos_id), 0)
+            if j:
+                pos[b], end[b], kept, out = p + j, p + j + 1, j, j
+            else:
+                tok = int(repl[b, a])
+                tokens[b, p + a + 1] = tok
+                pos[b], kept, out = p + a + 1, a, a + 1
+                if eos_id >= 0 and tok == eos_id:
+                    end[b] = p + a + 2
+            drafted[b] += n
+            accepted[b] += kept
+            emitted[b] += out
+            last_accept[b] = kept
+        if dpos is not None:
+            dpos.copy_(pos)
+            dend.copy_((end.clamp(max=S_max) - 1).clamp(min=0))
+        return
+    for t in (acc, repl, tokens):
+        assert t.is_contiguous()
+    rc = _lib.lib().jdt_spec_commit(_ptr(acc), _ptr(repl), B, C, _ptr(tokens), S_max, _ptr(pos), _ptr(end),
+                                    _ptr(count), int(eos_id), _ptr(drafted), _ptr(accepted), _ptr(emitted),
+                                    _ptr(last_accept), _ptr(dpos), _ptr(dend), _lib.stream_ptr())
+    _lib.check(rc, "jdt_spec_commit")
+
+
 # ----------------------------------------------------------------------------- beam search (csrc/beam.hip)
-BEAM_MAX_W = 8   # beams per group == entries per row of the candidate scratch (csrc/beam.hip BM_MAXW)
+BEAM_MAX_W = 8  # beams per group == entries per row of the candidate scratch (csrc/beam.hip BM_MAXW)
 
 
 def cache_ptr_table(tensors):

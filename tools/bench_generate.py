@@ -4,6 +4,7 @@ eagerly against one captured step replayed per token, plus the kernel-launcher c
 
     python tools/bench_generate.py [--steps 100] [--temperature 0.0] [--ragged] [--seq-len N] [--prompt-len P]
                                    [--prefill-chunk N[,N...]] [--split-append] [--beams W[,W...]]
+                                   [--speculative K[,K...]]
 
 Each figure: ``--steps`` decode steps after a 16-token prefill, timed with events around the
 whole loop (prefill excluded), median of 5 runs.  ``--seq-len N`` > 128 builds the LM with an
@@ -18,7 +19,12 @@ and through chunked prefill at each chunk size (``prefill_lines``); with ``--spl
 line is followed by a ``chunk N split`` line, the same prefill through the split-KV append attention
 of ``Generator(..., split_append=True)``.  ``--beams 4,8`` adds, per batch
 size G (then the number of prompts) and beam count W, the beam step of ``Generator.beam_search`` on G x W
-rows beside the plain sampled step at the same batch and depth (``beam_lines``).
+rows beside the plain sampled step at the same batch and depth (``beam_lines``).  ``--speculative 2,4,8``
+adds, per batch size and draft count K, the captured speculative round of ``Generator.spec_step`` beside
+the plain captured step of the main line: us per round, tokens per round and hence us per token, for the
+target itself as the draft (acceptance near 1: the ceiling on tokens per round, at the full cost of K + 1
+target-sized draft steps) and for a 1-layer draft with fresh weights (acceptance near 0: one token per
+round, the worst case) (``spec_lines``).
 """
 import argparse
 import os
@@ -169,8 +175,53 @@ def beam_lines(model, P, G, dev, beams, steps, temperature, depth):
         del gen, graph, pgraph, reset, preset
 
 
+def spec_lines(model, P, B, dev, ks, steps, temperature, depth, t_plain):
+    """Per draft count k and draft -- the target itself, then a 1-layer LM with fresh weights: us per
+    captured speculative round (k + 1 draft steps, the count, the verify append pass, judge, commit),
+    the tokens a row emits per round (from the device counters over the timed number of rounds) and
+    the resulting us per token beside the plain captured step's ``t_plain``; and the launcher calls
+    of one round.  Rounds per run: ``steps // (k + 1)``, so no row reaches its end while timed."""
+    cfg = model.cfg
+    small = TransformerLM(TransformerConfig(seq_len=cfg.seq_len, n_layers=1))
+    drafts = (("self", (model, P)), ("1-layer", (small, FlatParams(small.param_specs(), device=dev).init_(1))))
+    prompt = torch.randint(0, cfg.vocab_size, (B, PROMPT), generator=torch.Generator().manual_seed(1))
+    prompt = prompt.to(torch.int32).to(dev)
+    for k in ks:
+        rounds = max(steps // (k + 1), 1)
+        for name, draft in drafts:
+            gen = Generator(model, P, B, dev, draft=draft)
+            gen.generate(prompt, 2 * (k + 1), temperature=temperature, speculative=k, capture=True)   # warm-up + capture
+            graph = gen._graphs[("spec", k, float(temperature), 0, 0, 1.0, -1)][0]
+            st = gen.spec_state(k)
+
+            def reset():
+                gen.generate(prompt, 0, temperature=temperature, speculative=k)   # both prefills, in sync, no round
+                gen.kv.end.fill_(min(PROMPT + steps + 2, cfg.seq_len))
+                gen.draft.kv.end.copy_(gen.kv.end - 1)
+
+            step = lambda: gen.spec_step(k)  # noqa: E731
+            reset()
+            calls = launches_per_step(gen, step)
+            run = graph.replay if graph is not None else step
+            t_r = timed(run, reset, rounds)
+            reset()
+            for _ in range(rounds):
+                run()
+            per_round = float(st.emitted.sum()) / (B * rounds)
+            acc, dr = int(st.accepted.sum()), int(st.drafted.sum())
+            print(f"spec     B={B:2d} T={temperature}{depth} k={k:2d} draft={name:>7}: "
+                  f"{'captured' if graph is not None else 'eager'} {t_r:8.1f} us/round | {per_round:5.2f} tokens/round "
+                  f"(accepted / drafted {acc} / {dr}) | {t_r / per_round:7.1f} us/token (plain captured step "
+                  f"{t_plain:7.1f}) | {sum(calls.values())} launcher calls/round: "
+                  + ", ".join(f"{c[4:]} x{v}" for c, v in sorted(calls.items())), flush=True)
+            del gen, graph, st, reset, step, run
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--speculative", default=None, metavar="K[,K...]",
+                    help="extra lines per batch size: the captured speculative round with K drafts, for the target "
+                         "as its own draft and for a fresh 1-layer draft, beside the plain captured step")
     ap.add_argument("--beams", default=None, metavar="W[,W...]",
                     help="extra lines per batch size G: the beam step on G x W rows, eager and captured, beside "
                          "the plain sampled step at the same batch")
@@ -210,11 +261,14 @@ def main():
         depth = f" S={a.seq_len} P={PROMPT}" if a.seq_len != 128 or a.prompt_len is not None else ""
         line = (f"generate B={B:2d} T={a.temperature}{depth}: eager {t_e:7.1f} us/step "
                 f"({B / t_e * 1e6:9.0f} tokens/s)")
+        t_g = float("nan")
         if graph is not None:
             t_g = timed(graph.replay, reset, a.steps)
             line += f" | captured {t_g:7.1f} us/step ({B / t_g * 1e6:9.0f} tokens/s)"
         print(line + f" | {sum(calls.values())} launcher calls/step: "
               + ", ".join(f"{k[4:]} x{v}" for k, v in sorted(calls.items())), flush=True)
+        if a.speculative:
+            spec_lines(model, P, B, dev, [int(v) for v in a.speculative.split(",")], a.steps, a.temperature, depth, t_g)
         if a.prefill_chunk:
             del gen, graph, reset
             prefill_lines(model, P, B, dev, prompt, [int(v) for v in a.prefill_chunk.split(",")],
