@@ -11,6 +11,7 @@ one captured decode step replayed per token).
     python generate.py --seq-len 4096 --prompt-len 4000 --prefill-chunk 64 --split-append   # split-KV append
     python generate.py --beams 4 --length-penalty 1.0 --eos-id 7              # beam search, 4 hypotheses per prompt
     python generate.py --train-steps 200 --speculative 4 --draft-layers 1     # speculative decoding, 4 drafts per round
+    python generate.py --seq-len 4096 --prompt-len 4000 --kv-dtype fp8        # FP8 KV cache: 68 bytes per row, not 128
 
 Runs the HIP kernels on a GPU and the torch reference paths on CPU tensors when none is
 present.  The prompt is the first ``--prompt-len`` tokens of ``lm_batch``'s sequences;
@@ -28,7 +29,11 @@ best first with their scores, ranked by ``log-probability / length ** --length-p
 layers (default 1; the same width, vocabulary and ``--seq-len``, trained for the same ``--train-steps`` on
 the same batch) proposes K greedy tokens per round and the target scores them in one append pass; the
 output distribution is the plain decoder's.  The run also prints the rounds and accepted / drafted.
-Not covered: sampled, n-gram or tree drafters, speculative beams, beams over ragged prompts, diverse or constrained beam search, repetition penalties,
+``--kv-dtype fp8`` stores the cache as e4m3 bytes with one power-of-two fp32 scale per (layer, head, token) row of
+K and of V (68 bytes against 128); attention then sees the dequantized rows.  Not with ``--beams``,
+``--speculative`` or ``--split-append``.
+Not covered: FP8 caches with beams, speculative decoding or split append, per-channel or per-tensor scales,
+e5m2, FP8 MFMA for Q K^T, quantized weights, sampled, n-gram or tree drafters, speculative beams, beams over ragged prompts, diverse or constrained beam search, repetition penalties,
 sequences past ``seq_len``, caches longer than 32768 rows or head dims other than 64 on the HIP path,
 multi-GPU or pipeline-split generation.
 """
@@ -76,7 +81,11 @@ def parse_args(argv=None):
                     help="speculative decoding: K greedy drafts per round (1..15) from a small draft LM")
     ap.add_argument("--draft-layers", type=int, default=1, metavar="L",
                     help="with --speculative: layers of the draft LM (trained like the target)")
+    ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="the KV cache's storage: bf16, or fp8 (e4m3 bytes and one fp32 scale per row)")
     args = ap.parse_args(argv)
+    if args.kv_dtype == "fp8" and (args.beams or args.speculative or args.split_append):
+        ap.error("--kv-dtype fp8 does not combine with --beams, --speculative or --split-append")
     if args.speculative and args.beams:
         ap.error("--speculative and --beams exclude each other: there are no speculative beams")
     if args.speculative and not 1 <= args.speculative <= 15:
@@ -143,7 +152,8 @@ def main(args):
     if args.beams:
         return beam_main(args, tr, prompt, dev)
     draft = (trainers[1].state.apply_fn, trainers[1].state.params) if args.speculative else None
-    gen = Generator(tr.state.apply_fn, tr.state.params, args.batch, dev, split_append=args.split_append, draft=draft)
+    gen = Generator(tr.state.apply_fn, tr.state.params, args.batch, dev, split_append=args.split_append, draft=draft,
+                    kv_dtype=args.kv_dtype)
     sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
     kw = dict(temperature=args.temperature, seed=args.seed, capture=not args.eager, prompt_lens=lens,
               top_k=args.top_k, top_p=args.top_p, eos_id=args.eos_id, prefill_chunk=args.prefill_chunk)
@@ -161,7 +171,7 @@ def main(args):
     n = sum(lengths) - (int(lens.sum()) if lens is not None else args.batch * args.prompt_len)   # new tokens
     print(f"[generate] device={dev} batch={args.batch} prompt={args.prompt_lens or args.prompt_len} "
           f"new={args.max_new_tokens} temperature={args.temperature} top_k={args.top_k} top_p={args.top_p} "
-          f"eos_id={args.eos_id} {'eager' if args.eager or dev.type != 'cuda' else 'captured'}: "
+          f"eos_id={args.eos_id} kv_dtype={args.kv_dtype} ({gen.kv.cache_bytes() / 2 ** 20:.2f} MiB) {'eager' if args.eager or dev.type != 'cuda' else 'captured'}: "
           f"{n / dt:.1f} tokens/s ({dt * 1e3:.2f} ms with the prefill)")
     if args.speculative:
         acc, dr = int(gen.spec_accepted.sum()), int(gen.spec_drafted.sum())

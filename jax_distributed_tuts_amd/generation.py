@@ -3,7 +3,7 @@ training forward or in chunks straight into the cache, and a decode step of one 
 sequence.
 
 Cache layout: per layer K and V are ``[B, H, seq_len, 64]`` bf16 (a head's keys are
-contiguous 128-byte rows), ``tokens`` is ``int32 [B, seq_len]`` and ``pos`` is a device
+contiguous 128-byte rows; "FP8 cache" below: 64-byte rows and a scale), ``tokens`` is ``int32 [B, seq_len]`` and ``pos`` is a device
 ``int32[1]``: the number of tokens already in the cache, which is also the index of the
 token the next step processes.  Every kernel of a step reads ``pos`` from memory and the
 sampler -- the step's last launch -- advances it, so one captured step replays for every
@@ -76,7 +76,29 @@ rows >= ``pos``; those rows are rewritten before they are read, because the next
 from ``pos``.  ``verify(count)`` is the round without the drafter, for drafts the caller wrote into
 ``kv.tokens``: the hook for other drafters.
 
-Out of scope: sampled drafts with a q / p ratio test, n-gram / prompt-lookup or tree drafters (``verify``
+FP8 cache (``Generator(..., kv_dtype="fp8")``, opt-in; bf16 is untouched): K and V are stored as OCP e4m3
+bytes with one fp32 scale per cache row -- the 64 values of one (batch, head, token) of K or of V -- so a
+row takes 68 bytes against 128 (``KVCache.k`` / ``.v`` uint8 ``[B, H, seq_len, 64]``, ``.k_scale`` /
+``.v_scale`` fp32 ``[B, H, seq_len]``).  The format (``ops.kernels.kv_quantize`` is its definition, and the
+cache bytes are reproducible bit for bit on any device): ``amax = max |x|``, ``e = floor(log2(amax))``
+taken from amax's exponent bits and clamped to [-120, 127] (7 for a zero row), ``scale = 2^(e - 7)``,
+``q = e4m3fn(x * 2^(7 - e))`` rounded to nearest even.  The scale is a power of two, so the product is exact,
+the row's largest scaled magnitude lies in [128, 256) -- nothing reaches 448, no saturation -- and the
+dequantized ``float(q) * scale`` is exact in fp32 and exactly a bf16, within ``amax / 16`` of ``x``.
+Semantics: attention always sees the dequantized row.  The decode step quantizes the token's k / v, writes
+them and uses them as they will be read back; the append kernel does the same for the keys of its own
+chunk.  So the invariant above survives: the bits of token t's attention output depend only on ``(q_t,
+K[0..t], V[0..t])``, not on how the tokens were cut into calls.  The one exception is the default
+``prefill`` through the training forward: there the prompt rows attend over unquantized bf16 keys and only
+the cache is quantized (one launch of ``ops.kernels.kv_cache_fill`` per layer in the place of the two
+permute-copies) -- the usual arrangement; ``prefill(chunk=)`` has no such exception.  ``prefill`` in both
+forms, ``advance``, ``extend``, ``step`` and ``generate`` (shared and per-row positions, sampler filters, EOS,
+capture) run on an FP8 cache of up to 32768 rows through the ``_fp8`` launchers of csrc/attn_decode.hip and
+csrc/attn_append.hip, with the bf16 path's launches, chunks and workspaces; ``split_append=True``,
+``draft=`` and ``beam_begin`` / ``beam_search`` raise ``ValueError``.
+
+Out of scope: FP8 caches with beams, speculative decoding or split append, per-channel or per-tensor
+scales, e5m2, FP8 MFMA for Q K^T, quantized weights, sampled drafts with a q / p ratio test, n-gram / prompt-lookup or tree drafters (``verify``
 is the hook for them), speculative beams, continuing speculation after ``extend``, a draft with another
 vocabulary, adapting k per row or per round, beams over ragged prompts (per-row positions), diverse or
 constrained beam search, a beam cache that re-routes through an indirection table instead of copying,
@@ -100,6 +122,9 @@ from .parallel.step_program import capture_graph
 from .utils.flat import FlatParams
 
 
+KV_DTYPES = ("bf16", "fp8")
+
+
 class KVCache:
     """Per-layer K / V ``[B, H, seq_len, Dh]`` bf16, ``tokens`` int32 ``[B, seq_len]``, the
     device position word ``pos`` int32[1] and ``o``, the decode step's attention output
@@ -114,13 +139,27 @@ class KVCache:
     one-launch kernel.  Only ``Generator(split_append=True)`` allocates it, on first use and again
     when a larger slice needs more.  Size: 16.5 KiB (64 rows x 66 words) per (batch x head, 64-row
     query tile, 512-key span) -- 8.3 MiB at B = 1, H = 8, chunk 64 and ``seq_len`` 32768, and it
-    scales with the chunk and the batch."""
+    scales with the chunk and the batch.
+    ``kv_dtype="fp8"``: ``k`` / ``v`` are uint8 (e4m3 bytes, 64 per row) and ``k_scale`` / ``v_scale`` hold
+    per layer the rows' scales, fp32 ``[B, H, seq_len]`` initialised to 1 -- 68 bytes per row against 128.
+    ``"bf16"``: ``k_scale`` / ``v_scale`` are ``None``."""
 
-    def __init__(self, cfg: TransformerConfig, batch: int, device):
+    def __init__(self, cfg: TransformerConfig, batch: int, device, kv_dtype: str = "bf16"):
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
         H, Dh = cfg.n_heads, cfg.d_model // cfg.n_heads
-        mk = lambda: torch.zeros(batch, H, cfg.seq_len, Dh, dtype=torch.bfloat16, device=device)  # noqa: E731
+        self.kv_dtype = kv_dtype
+        fp8 = kv_dtype == "fp8"
+        if fp8 and Dh != K.KV_ROW:
+            raise ValueError(f"an FP8 cache needs head dim {K.KV_ROW} (the quantized row), got {Dh}")
+        mk = lambda: torch.zeros(batch, H, cfg.seq_len, Dh, dtype=torch.uint8 if fp8 else torch.bfloat16,  # noqa: E731
+                                 device=device)
         self.k = [mk() for _ in range(cfg.n_layers)]
         self.v = [mk() for _ in range(cfg.n_layers)]
+        # FP8: one fp32 power-of-two scale per cache row (1: the scale of a zero row)
+        sc = lambda: torch.ones(batch, H, cfg.seq_len, dtype=torch.float32, device=device)  # noqa: E731
+        self.k_scale = [sc() for _ in range(cfg.n_layers)] if fp8 else None
+        self.v_scale = [sc() for _ in range(cfg.n_layers)] if fp8 else None
         self.tokens = torch.zeros(batch, cfg.seq_len, dtype=torch.int32, device=device)
         self.pos = torch.zeros(1, dtype=torch.int32, device=device)
         self.pos_rows = torch.zeros(batch, dtype=torch.int32, device=device)
@@ -138,6 +177,11 @@ class KVCache:
     @property
     def live_pos(self) -> torch.Tensor:
         return self.pos_rows if self.per_row else self.pos
+
+    def cache_bytes(self) -> int:
+        """Bytes of every layer's K and V with their scales: 2 * L * B * H * seq_len * 128 for bf16, * 68 for FP8."""
+        ts = self.k + self.v + (self.k_scale or []) + (self.v_scale or [])
+        return sum(t.numel() * t.element_size() for t in ts)
 
     def history_ptrs(self):
         """``ops.kernels.cache_ptr_table`` of every layer's K, then V: the table the beam reorder's one
@@ -198,15 +242,25 @@ class Generator:
     ``beam_search(prefill_chunk=)`` -- runs the split-KV append attention (``KVCache.append_ws``
     holds its partials) instead of the one-launch kernel.  ``draft`` = (draft_model, draft_P): the
     drafter of speculative decoding, a full ``TransformerLM`` of the same ``vocab_size`` and
-    ``seq_len`` (``self.draft`` is its ``Generator``; its ``kv.tokens`` is this one's tensor)."""
+    ``seq_len`` (``self.draft`` is its ``Generator``; its ``kv.tokens`` is this one's tensor).
+    ``kv_dtype="fp8"`` (opt-in): the cache is quantized (``KVCache``, the module docstring has the
+    format and the semantics); ``prefill`` in both forms, ``advance``, ``extend``, ``step`` and
+    ``generate`` work as on a bf16 cache, while ``split_append=True``, ``draft=`` and ``beam_begin`` /
+    ``beam_search`` raise ``ValueError``."""
 
     def __init__(self, model: TransformerLM, P: FlatParams, batch: int, device, split_append: bool = False,
-                 draft=None):
+                 draft=None, kv_dtype: str = "bf16"):
         if not (model.has_embed and model.has_head and list(model.layers) == list(range(model.cfg.n_layers))):
             raise ValueError("Generator needs the full model (embedding, every layer and the head): "
                              "pipeline-split stages cannot generate")
+        if kv_dtype == "fp8" and split_append:
+            raise ValueError("kv_dtype='fp8' does not support split_append=True (the split append launchers take "
+                             "bf16 caches only)")
+        if kv_dtype == "fp8" and draft is not None:
+            raise ValueError("kv_dtype='fp8' does not support draft= (speculative decoding runs on bf16 caches only)")
         self.model, self.P, self.batch, self.device = model, P, int(batch), torch.device(device)
-        self.kv = KVCache(model.cfg, self.batch, self.device)
+        self.kv_dtype = kv_dtype
+        self.kv = KVCache(model.cfg, self.batch, self.device, kv_dtype=kv_dtype)
         self.split_append = bool(split_append)
         self.x =torch.zeros(self.batch, model.cfg.d_model, dtype=torch.bfloat16, device=self.device)
         self.temperature, self.seed = 0.0, 0
@@ -299,6 +353,9 @@ class Generator:
         self.prefill_rows = Sp
         _, cache = model.forward(self.P, kv.tokens if Sp == c.seq_len else kv.tokens[:, :Sp].contiguous())
         for l, bc in zip(self.model.layers, cache.blocks):
+            if kv.k_scale is not None:   # FP8: one quantizing launch per layer instead of the two copies
+                K.kv_cache_fill(bc.qkv, kv.k[l], kv.v[l], kv.k_scale[l], kv.v_scale[l], Pn, Sp)
+                continue
             qkv = bc.qkv.view(B, Sp, 3, H, Dh)
             kv.k[l][:, :, :Pn] = qkv[:, :Pn, 1].permute(0, 2, 1, 3)
             kv.v[l][:, :, :Pn] = qkv[:, :Pn, 2].permute(0, 2, 1, 3)
@@ -672,6 +729,8 @@ class Generator:
         """Start a beam search: ``prompt`` int [G, P] with G * num_beams == batch is repeated over each
         group's slots and prefilled (shared position, pos = P - 1), and the beam state is reset.
         Returns the ``BeamState`` (also ``self.beam``); ``beam_step`` runs the steps."""
+        if self.kv_dtype == "fp8":
+            raise ValueError("kv_dtype='fp8' does not support beam search (the cache reorder moves bf16 rows only)")
         c, W = self.model.cfg, int(num_beams)
         if not 1 <= W <= K.BEAM_MAX_W:
             raise ValueError(f"num_beams must be in 1..{K.BEAM_MAX_W}, got {num_beams}")

@@ -216,7 +216,8 @@ class TransformerLM:
         ``kv.pos`` (``ops.kernels.embed_decode``), ``kv`` a ``generation.KVCache``; returns
         the logits [B, vocab] bf16.  The same ``ln_gemm`` / ``gemm`` calls as ``forward`` at
         M = B, with ``attention_decode`` (appends to layer l's cache, attends over rows
-        0..pos; past 128 cache rows its partials go through ``kv.split_ws``) in the place of
+        0..pos; past 128 cache rows its partials go through ``kv.split_ws``; an FP8 cache's
+        ``kv.k_scale`` / ``kv.v_scale`` select the quantizing kernels) in the place of
         ``attention_fwd``.  The position is the cache's live tensor:
         ``kv.pos_rows`` (one word per sequence) when ``kv.per_row`` is set, else ``kv.pos``; it
         is only read."""
@@ -230,7 +231,9 @@ class TransformerLM:
             b = f"block_{l}"
             qkv, _, _, _ = K.ln_gemm(h, P.p(f"{b}/ln1/scale"), P.p(f"{b}/ln1/bias"), P.s(f"{b}/attn/qkv/kernel"),
                                      eps=c.ln_eps, bias=P.s(f"{b}/attn/qkv/bias"))
-            o = K.attention_decode(qkv, kv.k[l], kv.v[l], pos, c.n_heads, out=kv.o, ws=getattr(kv, "split_ws", None))
+            ks, vs = getattr(kv, "k_scale", None), getattr(kv, "v_scale", None)   # an FP8 cache's row scales
+            o = K.attention_decode(qkv, kv.k[l], kv.v[l], pos, c.n_heads, out=kv.o, ws=getattr(kv, "split_ws", None),
+                                   k_scale=None if ks is None else ks[l], v_scale=None if vs is None else vs[l])
             x2 = K.gemm(o, P.s(f"{b}/attn/out/kernel"), bias=P.s(f"{b}/attn/out/bias"), resid=h)
             # z_out as in forward: the GELU then sees the pre-activation rounded to bf16
             z1 = torch.empty(x2.shape[0], c.d_ff, dtype=torch.bfloat16, device=x2.device)
@@ -267,8 +270,10 @@ class TransformerLM:
             # per-row counts: rows past a sequence's count keep the zeros (finite inputs for the GEMMs below)
             mk = torch.empty if count is None else torch.zeros
             o = mk(h.shape[0], c.d_model, dtype=torch.bfloat16, device=h.device)
+            ks, vs = getattr(kv, "k_scale", None), getattr(kv, "v_scale", None)   # an FP8 cache's row scales
             K.attention_append(qkv, kv.k[l], kv.v[l], pos, c.n_heads, C, count=count, out=o,
-                               ws=getattr(kv, "append_ws", None))
+                               ws=getattr(kv, "append_ws", None), k_scale=None if ks is None else ks[l],
+                               v_scale=None if vs is None else vs[l])
             x2 = K.gemm(o, P.s(f"{b}/attn/out/kernel"), bias=P.s(f"{b}/attn/out/bias"), resid=h)
             z1 = torch.empty(x2.shape[0], c.d_ff, dtype=torch.bfloat16, device=x2.device)
             u, _, _, _ = K.ln_gemm(x2, P.p(f"{b}/ln2/scale"), P.p(f"{b}/ln2/bias"), P.s(f"{b}/mlp/fc1/kernel"),

@@ -146,6 +146,26 @@ _SIGS = {
                                       c_int, c_int, c_int, c_float, c_void_p]),
     "jdt_attn_append_split_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    # FP8 KV cache (csrc/kv_fp8.h): the bf16 launchers' lists with k_scale, v_scale after the caches
+    # (qkv, k_cache, v_cache, k_scale, v_scale, o, pos, B, H, Dh, S_max, scale, stream)
+    "jdt_attn_decode_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_int, c_int, c_int, c_float, c_void_p]),
+    "jdt_attn_decode_fp8_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                         c_int, c_int, c_int, c_float, c_void_p]),
+    # (qkv, k_cache, v_cache, k_scale, v_scale, o, pos, ws, ws_floats, B, H, Dh, S_max, scale, stream)
+    "jdt_attn_decode_fp8_long": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_long, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "jdt_attn_decode_fp8_long_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_long, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    # (qkv, k_cache, v_cache, k_scale, v_scale, o, pos, B, C, H, Dh, S_max, scale, stream); per row: (..., pos,
+    # count, B, ...)
+    "jdt_attn_append_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    "jdt_attn_append_fp8_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
+    # csrc/kv_quantize.hip: (qkv, k_cache, v_cache, k_scale, v_scale, B, H, Dh, S_max, Sp, n, stream)
+    "jdt_kv_quantize_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                     c_int, c_int, c_void_p]),
     # (tokens, wte, wpe, out, pos, B, C, S_max, d, vocab, stream); per row: (..., pos, count, B, ...)
     "jdt_embed_append":(c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                  c_void_p]),

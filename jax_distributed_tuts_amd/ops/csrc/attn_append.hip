@@ -48,6 +48,7 @@
 // The spans are absolute and a fully masked tile is an exact no-op, so the cut invariance above
 // holds for the split pair too; the caches come out bit for bit as from the one-launch kernel.
 #include "attn_tile.h"
+#include "kv_fp8.h"
 
 #include <limits.h>
 
@@ -64,11 +65,23 @@ constexpr int AP_CB = 8;            // spans the combine loads at a time
 // One body for both launches, as attn_decode_kernel.  SPLIT (the split launch): blockIdx.z is the
 // span and ``out`` is the fp32 workspace instead of o, so <ROWS, false> keeps the one-launch
 // kernel's arguments and instruction stream.
-template <bool ROWS, bool SPLIT>
+//
+// FP8 (the ``_fp8`` launchers, one launch only; kv_fp8.h has the format): the caches are e4m3 bytes with
+// one fp32 scale per row in ``ksc`` / ``vsc`` [B, H, S_max].  The 8 consecutive threads that own a row's
+// eight chunks are an aligned lane octet: they quantize the row together.  The cache write stores the
+// tile's rows quantized; a key below p is fetched as 8 bytes plus its scale and a key of the chunk as its
+// qkv row, and both become the bf16x8 image of the DEQUANTIZED row (exact) just before staging -- the
+// chunk's keys through the quantizer, so a query sees them as every later call will read them back.
+// Staging, the tile body and the epilogue are the bf16 kernel's, and FP8 = false is that kernel (``ksc`` /
+// ``vsc`` are null and unused): every FP8 statement is under ``if constexpr``.
+template <bool ROWS, bool SPLIT, bool FP8>
 __global__ void __launch_bounds__(256)
-attn_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+attn_append_kernel(const bf16_t* __restrict__ qkv, std::conditional_t<FP8, uint8_t, bf16_t>* __restrict__ kc,
+                   std::conditional_t<FP8, uint8_t, bf16_t>* __restrict__ vc,
                    std::conditional_t<SPLIT, float, bf16_t>* __restrict__ out, const int* __restrict__ pos_ptr,
-                   const int* __restrict__ count, int C, int H, int S_max, float scale) {
+                   const int* __restrict__ count, int C, int H, int S_max, float scale, float* __restrict__ ksc,
+                   float* __restrict__ vsc) {
+  static_assert(!(FP8 && SPLIT), "the split launchers take bf16 caches only");
   __shared__ __attribute__((aligned(16))) bf16_t Ks[AT_T * AT_LD];
   __shared__ __attribute__((aligned(16))) bf16_t Vt[AT_D * AT_LD];
   __shared__ __attribute__((aligned(16))) bf16_t Ps[4][16 * AT_LD];
@@ -89,13 +102,39 @@ attn_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16
   const int d = H * AT_D;
   const long ld3 = 3L * d;
   const bf16_t* base = qkv + (long)b * C * ld3 + h * AT_D;   // token 0's q; + d: k; + 2 d: v
-  bf16_t* Kh = kc + (long)bh * S_max * AT_D;
-  bf16_t* Vh = vc + (long)bh * S_max * AT_D;
+  auto* Kh = kc + (long)bh * S_max * AT_D;
+  auto* Vh = vc + (long)bh * S_max * AT_D;
+  // FP8: the scales of this head's rows
+  float* Ksc = nullptr;
+  float* Vsc = nullptr;
+  if constexpr (FP8) {
+    Ksc = ksc + (long)bh * S_max;
+    Vsc = vsc + (long)bh * S_max;
+  }
 
   // this query tile's k / v rows -> cache rows p + q0 .. p + qn - 1 (SPLIT: span 0's workgroup alone)
   for (int c = threadIdx.x; c < AT_T * AT_D / 8; c += 256) {
     const int i = q0 + (c >> 3), dc = (c & 7) * 8;
-    if (i < qn && (!SPLIT || blockIdx.z == 0)) {
+    if constexpr (FP8) {
+      // every lane runs the quantizer (the loop's trip count is the same for all): a row past qn is zeros
+      const bool own = i < qn;   // the same in the row's octet
+      const bf16_t* src = base + (long)i * ld3 + dc;
+      u32x4 kx = {0u, 0u, 0u, 0u}, vx = kx;
+      if (own) {
+        kx = *reinterpret_cast<const u32x4*>(src + d);
+        vx = *reinterpret_cast<const u32x4*>(src + 2 * d);
+      }
+      float ksv, vsv;
+      const u32x2 kq = kv_quantize8(kx, ksv), vq = kv_quantize8(vx, vsv);
+      if (own) {
+        *reinterpret_cast<u32x2*>(Kh + (long)(p + i) * AT_D + dc) = kq;
+        *reinterpret_cast<u32x2*>(Vh + (long)(p + i) * AT_D + dc) = vq;
+        if (dc == 0) {
+          Ksc[p + i] = ksv;
+          Vsc[p + i] = vsv;
+        }
+      }
+    } else if (i < qn && (!SPLIT || blockIdx.z == 0)) {
       const bf16_t* src = base + (long)i * ld3 + dc;
       *reinterpret_cast<u32x4*>(Kh + (long)(p + i) * AT_D + dc) = *reinterpret_cast<const u32x4*>(src + d);
       *reinterpret_cast<u32x4*>(Vh + (long)(p + i) * AT_D + dc) = *reinterpret_cast<const u32x4*>(src + 2 * d);
@@ -111,12 +150,45 @@ attn_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16
       kr[j] = (u32x4){0u, 0u, 0u, 0u};
       vr[j] = kr[j];
       if (key < p) {   // < p <= S_max: from the cache
-        kr[j] = *reinterpret_cast<const u32x4*>(Kh + (long)key * AT_D + dc);
-        vr[j] = *reinterpret_cast<const u32x4*>(Vh + (long)key * AT_D + dc);
+        if constexpr (FP8) {   // the raw image: 8 bytes, then the row's scale; dequant() below opens it
+          const u32x2 k8 = *reinterpret_cast<const u32x2*>(Kh + (long)key * AT_D + dc);
+          const u32x2 v8 = *reinterpret_cast<const u32x2*>(Vh + (long)key * AT_D + dc);
+          kr[j] = (u32x4){k8[0], k8[1], __float_as_uint(Ksc[key]), 0u};
+          vr[j] = (u32x4){v8[0], v8[1], __float_as_uint(Vsc[key]), 0u};
+        } else {
+          kr[j] = *reinterpret_cast<const u32x4*>(Kh + (long)key * AT_D + dc);
+          vr[j] = *reinterpret_cast<const u32x4*>(Vh + (long)key * AT_D + dc);
+        }
       } else if (key < kend) {   // chunk token key - p < qn <= C: from qkv, never from the cache
         const bf16_t* src = base + (long)(key - p) * ld3 + dc;
         kr[j] = *reinterpret_cast<const u32x4*>(src + d);
         vr[j] = *reinterpret_cast<const u32x4*>(src + 2 * d);
+      }
+    }
+  };
+  // FP8: what fetch(k0) left -> the bf16x8 images of the dequantized rows.  Kept apart from fetch so
+  // that the loads stay in flight over the previous tile's MFMA work.  Every lane runs the quantizer
+  // (a row that is not a chunk key goes through as zeros); the case is the same in a row's octet.
+  auto dequant = [&](int k0) {
+    const bool below = k0 + AT_T <= p;   // the whole tile comes from the cache (uniform): no quantizer
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int key = k0 + ((threadIdx.x + 256 * j) >> 3);
+      const bool cached = key < p, fresh = !cached && key < kend;
+      const u32x4 zero = {0u, 0u, 0u, 0u};
+      u32x4 kd = zero, vd = zero;
+      if (!below) {
+        float ksv, vsv;
+        const u32x2 kq = kv_quantize8(fresh ? kr[j] : zero, ksv), vq = kv_quantize8(fresh ? vr[j] : zero, vsv);
+        kd = kv_dequantize8(kq, ksv);
+        vd = kv_dequantize8(vq, vsv);
+      }
+      if (cached) {
+        kr[j] = kv_dequantize8((u32x2){kr[j][0], kr[j][1]}, __uint_as_float(kr[j][2]));
+        vr[j] = kv_dequantize8((u32x2){vr[j][0], vr[j][1]}, __uint_as_float(vr[j][2]));
+      } else {
+        kr[j] = kd;   // zeros past kend
+        vr[j] = vd;
       }
     }
   };
@@ -143,6 +215,7 @@ attn_append_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc, bf16
   fetch(kbeg);
   for (int k0 = kbeg; k0 < kstop; k0 += AT_T) {
     __syncthreads();   // the previous tile's readers are done with Ks / Vt
+    if constexpr (FP8) dequant(k0);
     stage();
     __syncthreads();
     if (k0 + AT_T < kstop) fetch(k0 + AT_T);
@@ -246,9 +319,10 @@ static int attn_append_launch(const void* qkv, void* k_cache, void* v_cache, voi
   if (!qkv || !k_cache || !v_cache || !o || !pos || (ROWS && !count)) return -2;
   if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
   if (B == 0) return 0;
-  hipLaunchKernelGGL((attn_append_kernel<ROWS, false>), dim3((C + AT_T - 1) / AT_T, B * H), dim3(256), 0,
+  hipLaunchKernelGGL((attn_append_kernel<ROWS, false, false>), dim3((C + AT_T - 1) / AT_T, B * H), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(k_cache),
-                     static_cast<bf16_t*>(v_cache), static_cast<bf16_t*>(o), pos, count, C, H, S_max, scale);
+                     static_cast<bf16_t*>(v_cache), static_cast<bf16_t*>(o), pos, count, C, H, S_max, scale,
+                     static_cast<float*>(nullptr), static_cast<float*>(nullptr));
   return HIP_LAUNCH_CHECK();
 }
 
@@ -263,6 +337,44 @@ JDT_API int jdt_attn_append(const void* qkv, void* k_cache, void* v_cache, void*
 JDT_API int jdt_attn_append_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos,
                                  const int* count, int B, int C, int H, int Dh, int S_max, float scale, void* stream) {
   return attn_append_launch<true>(qkv, k_cache, v_cache, o, pos, count, B, C, H, Dh, S_max, scale, stream);
+}
+
+// The FP8 launchers: attn_append_launch's checks and codes, with -2 also for a null scale pointer and -6
+// for caches off an 8-byte or scales off a 4-byte boundary.
+template <bool ROWS>
+static int attn_append_fp8_launch(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                  void* o, const int* pos, const int* count, int B, int C, int H, int Dh, int S_max,
+                                  float scale, void* stream) {
+  if (Dh != AT_D) return -3;
+  if (S_max < 1 || S_max > AP_SMAX) return -4;
+  if (C < 1 || C > AP_CMAX) return -11;
+  if (B < 0 || H < 1 || (long)B * H > 65535) return -5;
+  if (!qkv || !k_cache || !v_cache || !k_scale || !v_scale || !o || !pos || (ROWS && !count)) return -2;
+  if (misaligned16(qkv) || misaligned8(k_cache) || misaligned8(v_cache) || misaligned4(k_scale) ||
+      misaligned4(v_scale))
+    return -6;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL((attn_append_kernel<ROWS, false, true>), dim3((C + AT_T - 1) / AT_T, B * H), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
+                     static_cast<uint8_t*>(k_cache), static_cast<uint8_t*>(v_cache), static_cast<bf16_t*>(o), pos,
+                     count, C, H, S_max, scale, k_scale, v_scale);
+  return HIP_LAUNCH_CHECK();
+}
+
+// jdt_attn_append on an FP8 cache: caches [B, H, S_max, Dh] e4m3 bytes, k_scale / v_scale fp32 [B, H, S_max]
+JDT_API int jdt_attn_append_fp8(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                void* o, const int* pos, int B, int C, int H, int Dh, int S_max, float scale,
+                                void* stream) {
+  return attn_append_fp8_launch<false>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, nullptr, B, C, H, Dh, S_max,
+                                       scale, stream);
+}
+
+// one position and one token count (0..C) per sequence: pos int32[B], count int32[B]
+JDT_API int jdt_attn_append_fp8_rows(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                     void* o, const int* pos, const int* count, int B, int C, int H, int Dh,
+                                     int S_max, float scale, void* stream) {
+  return attn_append_fp8_launch<true>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, count, B, C, H, Dh, S_max,
+                                      scale, stream);
 }
 
 // Split-KV: the split launch, then the combine on the same stream.  The checks and codes of
@@ -281,9 +393,10 @@ static int attn_append_split_launch(const void* qkv, void* k_cache, void* v_cach
   const int n_qt = (C + AT_T - 1) / AT_T, n_spans = (S_max + AP_SPAN - 1) / AP_SPAN;
   if (ws_floats < (long)B * H * n_qt * n_spans * AT_T * AP_SLOT) return -10;
   if (B == 0) return 0;
-  hipLaunchKernelGGL((attn_append_kernel<ROWS, true>), dim3(n_qt, B * H, n_spans), dim3(256), 0,
+  hipLaunchKernelGGL((attn_append_kernel<ROWS, true, false>), dim3(n_qt, B * H, n_spans), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(k_cache),
-                     static_cast<bf16_t*>(v_cache), ws, pos, count, C, H, S_max, scale);
+                     static_cast<bf16_t*>(v_cache), ws, pos, count, C, H, S_max, scale, static_cast<float*>(nullptr),
+                     static_cast<float*>(nullptr));
   const int rc = HIP_LAUNCH_CHECK();
   if (rc) return rc;
   hipLaunchKernelGGL(attn_append_combine_kernel<ROWS>, dim3(n_qt, B * H), dim3(1024), 0,

@@ -28,9 +28,12 @@
 //               optionally restricted to the top-k / top-p set (FILT = true); the argmax, the
 //               threshold and the draw are row_select.h's, shared with the speculative judge
 #include "common.h"
+#include "kv_fp8.h"
 #include "row_select.h"
 
 #include <limits.h>
+
+#include <type_traits>
 
 namespace jdt {
 
@@ -67,11 +70,21 @@ __device__ __forceinline__ float oct_sum_dpp(float v) {
 // slot (bh, ch): the chunk's max m, l = sum exp(s - m) and the unnormalised fp32 o[64].
 // The grid, (B * H, ceil(S_max / AD_CHUNK)), depends on the cache's shape only, never on pos.
 // ``o`` is unused with SPLIT and ``ws`` without it.
-template <bool ROWS, bool SPLIT>
-__global__ void __launch_bounds__(256) attn_decode_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ kc,
-                                                         bf16_t* __restrict__ vc, bf16_t* __restrict__ o,
-                                                         const int* __restrict__ pos_ptr, int H, int S_max,
-                                                         float scale, float* __restrict__ ws) {
+//
+// FP8 (the ``_fp8`` launchers; kv_fp8.h has the format): the caches are e4m3 bytes, 64 per row, with one
+// fp32 power-of-two scale per row in ``ksc`` / ``vsc`` [B, H, S_max].  A lane's slice of a cached row is one
+// 8-byte load plus the row's scale word; the token's k / v are quantized in registers (amax over the key's
+// lane octet), one octet stores the 64 bytes and one lane each scale, and the workgroup itself uses the
+// token as it will be read back.  The bytes stay packed until their use; a row's scale goes on its score
+// and on its p instead of on its 8 values -- a power of two, so the same bits.  FP8 = false is the bf16
+// kernel (``ksc`` / ``vsc`` are null and unused): every FP8 statement is under ``if constexpr``.
+template <bool ROWS, bool SPLIT, bool FP8>
+__global__ void __launch_bounds__(256)
+attn_decode_kernel(const bf16_t* __restrict__ qkv, std::conditional_t<FP8, uint8_t, bf16_t>* __restrict__ kc,
+                   std::conditional_t<FP8, uint8_t, bf16_t>* __restrict__ vc, bf16_t* __restrict__ o,
+                   const int* __restrict__ pos_ptr, int H, int S_max, float scale, float* __restrict__ ws,
+                   float* __restrict__ ksc, float* __restrict__ vsc) {
+  using row_t = std::conditional_t<FP8, u32x2, u32x4>;   // a lane's 8 values of a row: 8 e4m3 or 8 bf16
   __shared__ float red_m[4], red_l[4], red_o[4][AD_DH];
   const int bh = blockIdx.x, b = bh / H, h = bh % H;
   const int tok_pos = pos_ptr[ROWS ? b : 0];
@@ -85,28 +98,70 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const bf16_t* __restri
   const u32x4 qv = *reinterpret_cast<const u32x4*>(row);
   const u32x4 kn = *reinterpret_cast<const u32x4*>(row + d);
   const u32x4 vn = *reinterpret_cast<const u32x4*>(row + 2 * d);
-  bf16_t* Kh = kc + (long)bh * S_max * AD_DH + c * 8;   // SPLIT: the chunk's first row
-  bf16_t* Vh = vc + (long)bh * S_max * AD_DH + c * 8;
+  auto* Kh = kc + (long)bh * S_max * AD_DH + c * 8;   // SPLIT: the chunk's first row
+  auto* Vh = vc + (long)bh * S_max * AD_DH + c * 8;
   if (SPLIT) {
     Kh += (long)row0 * AD_DH;
     Vh += (long)row0 * AD_DH;
   }
-  // every load of the step is issued before the first use; rows past pos are never read
-  u32x4 kr[AD_NP], vr[AD_NP];
-#pragma unroll
-  for (int i = 0; i < AD_NP; ++i) {
-    const int j = g + AD_KPP * i;
-    if (j < pos) {
-      kr[i] = *reinterpret_cast<const u32x4*>(Kh + (long)j * AD_DH);
-      vr[i] = *reinterpret_cast<const u32x4*>(Vh + (long)j * AD_DH);
-    } else {
-      kr[i] = kn;   // j == pos: the token itself; j > pos: masked below
-      vr[i] = vn;
-    }
+  // FP8: the scales of this head's rows (SPLIT: from the chunk's first row on)
+  float* Ksc = nullptr;
+  float* Vsc = nullptr;
+  if constexpr (FP8) {
+    Ksc = ksc + (long)bh * S_max + row0;
+    Vsc = vsc + (long)bh * S_max + row0;
   }
-  if ((!SPLIT || pos < AD_CHUNK) && g == (pos & (AD_KPP - 1))) {
-    *reinterpret_cast<u32x4*>(Kh + (long)pos * AD_DH) = kn;
-    *reinterpret_cast<u32x4*>(Vh + (long)pos * AD_DH) = vn;
+  // every load of the step is issued before the first use; rows past pos are never read
+  row_t kr[AD_NP], vr[AD_NP];
+  float ks[FP8 ? AD_NP : 1], vs[FP8 ? AD_NP : 1];   // FP8: the rows' scales
+  if constexpr (FP8) {
+    // the cache loads go out first; quantizing the token then waits for kn / vn (issued before them) only
+#pragma unroll
+    for (int i = 0; i < AD_NP; ++i) {
+      const int j = g + AD_KPP * i;
+      if (j < pos) {
+        kr[i] = *reinterpret_cast<const row_t*>(Kh + (long)j * AD_DH);
+        vr[i] = *reinterpret_cast<const row_t*>(Vh + (long)j * AD_DH);
+        ks[i] = Ksc[j];
+        vs[i] = Vsc[j];
+      }
+    }
+    // the token's rows as the cache will hold them: every octet has the whole row and quantizes it
+    float kts, vts;
+    const row_t kt = kv_quantize8(kn, kts), vt = kv_quantize8(vn, vts);
+#pragma unroll
+    for (int i = 0; i < AD_NP; ++i) {
+      if (g + AD_KPP * i >= pos) {   // j == pos: the token itself; j > pos: masked below
+        kr[i] = kt;
+        vr[i] = vt;
+        ks[i] = kts;
+        vs[i] = vts;
+      }
+    }
+    if ((!SPLIT || pos < AD_CHUNK) && g == (pos & (AD_KPP - 1))) {
+      *reinterpret_cast<row_t*>(Kh + (long)pos * AD_DH) = kt;
+      *reinterpret_cast<row_t*>(Vh + (long)pos * AD_DH) = vt;
+      if (c == 0) {
+        Ksc[pos] = kts;
+        Vsc[pos] = vts;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < AD_NP; ++i) {
+      const int j = g + AD_KPP * i;
+      if (j < pos) {
+        kr[i] = *reinterpret_cast<const u32x4*>(Kh + (long)j * AD_DH);
+        vr[i] = *reinterpret_cast<const u32x4*>(Vh + (long)j * AD_DH);
+      } else {
+        kr[i] = kn;   // j == pos: the token itself; j > pos: masked below
+        vr[i] = vn;
+      }
+    }
+    if ((!SPLIT || pos < AD_CHUNK) && g == (pos & (AD_KPP - 1))) {
+      *reinterpret_cast<u32x4*>(Kh + (long)pos * AD_DH) = kn;
+      *reinterpret_cast<u32x4*>(Vh + (long)pos * AD_DH) = vn;
+    }
   }
   float qf[8];
   unpack8(qv, qf);
@@ -114,10 +169,12 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const bf16_t* __restri
 #pragma unroll
   for (int i = 0; i < AD_NP; ++i) {
     float kf[8], dot = 0.f;
-    unpack8(kr[i], kf);
+    if constexpr (FP8) fp8_unpack8(kr[i], kf);
+    else unpack8(kr[i], kf);
 #pragma unroll
     for (int e = 0; e < 8; ++e) dot += qf[e] * kf[e];
     dot = oct_sum_dpp(dot);
+    if constexpr (FP8) dot *= ks[i];   // exact: a power of two
     s[i] = (g + AD_KPP * i <= pos) ? dot * scale : -INFINITY;
     m = fmaxf(m, s[i]);
   }
@@ -138,9 +195,14 @@ __global__ void __launch_bounds__(256) attn_decode_kernel(const bf16_t* __restri
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int i = 0; i < AD_NP; ++i) {
-    const float p = round_bf(s[i]);   // exp(s - m) as bf16; 1 / l goes on the fp32 sum, as in attn128.hip
+    float p = round_bf(s[i]);   // exp(s - m) as bf16; 1 / l goes on the fp32 sum, as in attn128.hip
     float vf[8];
-    unpack8(vr[i], vf);
+    if constexpr (FP8) {
+      fp8_unpack8(vr[i], vf);
+      p *= vs[i];   // exact: a power of two
+    } else {
+      unpack8(vr[i], vf);
+    }
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] += p * vf[e];
   }
@@ -335,9 +397,11 @@ static int attn_decode_launch(const void* qkv, void* k_cache, void* v_cache, voi
   if (!qkv || !k_cache || !v_cache || !o || !pos) return -2;
   if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
   if (B == 0) return 0;
-  hipLaunchKernelGGL((attn_decode_kernel<ROWS, false>), dim3(B * H), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache),
-                     static_cast<bf16_t*>(o), pos, H, S_max, scale, static_cast<float*>(nullptr));
+  hipLaunchKernelGGL((attn_decode_kernel<ROWS, false, false>), dim3(B * H), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
+                     static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache), static_cast<bf16_t*>(o), pos, H,
+                     S_max, scale, static_cast<float*>(nullptr), static_cast<float*>(nullptr),
+                     static_cast<float*>(nullptr));
   return HIP_LAUNCH_CHECK();
 }
 
@@ -366,10 +430,10 @@ static int attn_decode_long_launch(const void* qkv, void* k_cache, void* v_cache
   const int n_chunks = (S_max + AD_CHUNK - 1) / AD_CHUNK;
   if (ws_floats < (long)B * H * n_chunks * AD_SLOT) return -10;
   if (B == 0) return 0;
-  hipLaunchKernelGGL((attn_decode_kernel<ROWS, true>), dim3(B * H, n_chunks), dim3(256), 0,
+  hipLaunchKernelGGL((attn_decode_kernel<ROWS, true, false>), dim3(B * H, n_chunks), dim3(256), 0,
                      static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
                      static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache), static_cast<bf16_t*>(nullptr), pos,
-                     H, S_max, scale, ws);
+                     H, S_max, scale, ws, static_cast<float*>(nullptr), static_cast<float*>(nullptr));
   const int rc = HIP_LAUNCH_CHECK();
   if (rc) return rc;
   hipLaunchKernelGGL(attn_decode_combine_kernel<ROWS>, dim3(B * H), dim3(WAVE), 0, static_cast<hipStream_t>(stream),
@@ -389,6 +453,85 @@ JDT_API int jdt_attn_decode_long_rows(const void* qkv, void* k_cache, void* v_ca
                                       float* ws, long ws_floats, int B, int H, int Dh, int S_max, float scale,
                                       void* stream) {
   return attn_decode_long_launch<true>(qkv, k_cache, v_cache, o, pos, ws, ws_floats, B, H, Dh, S_max, scale, stream);
+}
+
+// The FP8 launchers: the bf16 ones' checks and codes, with -2 also for a null scale pointer and -6 for
+// caches off an 8-byte or scales off a 4-byte boundary.
+template <bool ROWS>
+static int attn_decode_fp8_launch(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                  void* o, const int* pos, int B, int H, int Dh, int S_max, float scale,
+                                  void* stream) {
+  if (Dh != AD_DH) return -3;
+  if (S_max < 1 || S_max > AD_SMAX) return -4;
+  if (B < 0 || H < 1) return -5;
+  if (!qkv || !k_cache || !v_cache || !k_scale || !v_scale || !o || !pos) return -2;
+  if (misaligned16(qkv) || misaligned8(k_cache) || misaligned8(v_cache) || misaligned4(k_scale) ||
+      misaligned4(v_scale))
+    return -6;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL((attn_decode_kernel<ROWS, false, true>), dim3(B * H), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
+                     static_cast<uint8_t*>(k_cache), static_cast<uint8_t*>(v_cache), static_cast<bf16_t*>(o), pos, H,
+                     S_max, scale, static_cast<float*>(nullptr), k_scale, v_scale);
+  return HIP_LAUNCH_CHECK();
+}
+
+// jdt_attn_decode on an FP8 cache: caches [B, H, S_max, Dh] e4m3 bytes, k_scale / v_scale fp32 [B, H, S_max]
+JDT_API int jdt_attn_decode_fp8(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                void* o, const int* pos, int B, int H, int Dh, int S_max, float scale,
+                                void* stream) {
+  return attn_decode_fp8_launch<false>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, B, H, Dh, S_max, scale,
+                                       stream);
+}
+
+// as jdt_attn_decode_fp8 with one position per sequence: pos int32[B]
+JDT_API int jdt_attn_decode_fp8_rows(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                     void* o, const int* pos, int B, int H, int Dh, int S_max, float scale,
+                                     void* stream) {
+  return attn_decode_fp8_launch<true>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, B, H, Dh, S_max, scale,
+                                      stream);
+}
+
+// Split-KV on an FP8 cache: the same 128-key chunks, workspace and combine as the bf16 pair.
+template <bool ROWS>
+static int attn_decode_fp8_long_launch(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                       void* o, const int* pos, float* ws, long ws_floats, int B, int H, int Dh,
+                                       int S_max, float scale, void* stream) {
+  if (Dh != AD_DH) return -3;
+  if (S_max < 1 || S_max > AD_LONG_SMAX) return -4;
+  if (B < 0 || H < 1 || (long)B * H > INT_MAX) return -5;
+  if (!qkv || !k_cache || !v_cache || !k_scale || !v_scale || !o || !pos || !ws) return -2;
+  if (misaligned16(qkv) || misaligned8(k_cache) || misaligned8(v_cache) || misaligned4(k_scale) ||
+      misaligned4(v_scale))
+    return -6;
+  const int n_chunks = (S_max + AD_CHUNK - 1) / AD_CHUNK;
+  if (ws_floats < (long)B * H * n_chunks * AD_SLOT) return -10;
+  if (B == 0) return 0;
+  hipLaunchKernelGGL((attn_decode_kernel<ROWS, true, true>), dim3(B * H, n_chunks), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
+                     static_cast<uint8_t*>(k_cache), static_cast<uint8_t*>(v_cache), static_cast<bf16_t*>(nullptr),
+                     pos, H, S_max, scale, ws, k_scale, v_scale);
+  const int rc = HIP_LAUNCH_CHECK();
+  if (rc) return rc;
+  hipLaunchKernelGGL(attn_decode_combine_kernel<ROWS>, dim3(B * H), dim3(WAVE), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const float*>(ws), static_cast<bf16_t*>(o), pos, H, S_max, n_chunks);
+  return HIP_LAUNCH_CHECK();
+}
+
+// jdt_attn_decode_long on an FP8 cache
+JDT_API int jdt_attn_decode_fp8_long(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                     void* o, const int* pos, float* ws, long ws_floats, int B, int H, int Dh,
+                                     int S_max, float scale, void* stream) {
+  return attn_decode_fp8_long_launch<false>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, ws, ws_floats, B, H, Dh,
+                                            S_max, scale, stream);
+}
+
+// as jdt_attn_decode_fp8_long with one position per sequence: pos int32[B]
+JDT_API int jdt_attn_decode_fp8_long_rows(const void* qkv, void* k_cache, void* v_cache, float* k_scale,
+                                          float* v_scale, void* o, const int* pos, float* ws, long ws_floats, int B,
+                                          int H, int Dh, int S_max, float scale, void* stream) {
+  return attn_decode_fp8_long_launch<true>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, ws, ws_floats, B, H, Dh,
+                                           S_max, scale, stream);
 }
 
 template <bool ROWS>

@@ -1040,12 +1040,83 @@ def _per_row(pos: torch.Tensor, B: int) -> bool:
     return pos.numel() != 1
 
 
-def _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out):
-    """Composed torch path (any head dim / cache length, any device): reads ``pos`` on the host."""
+# ----------------------------------------------------------------------------- FP8 KV cache rows
+# The format of a quantized cache row -- the 64 values of one (batch, head, token) of K or of V -- defined
+# so that the cache bytes are reproducible bit for bit on any device.  These two functions ARE the
+# definition; the HIP kernels (csrc/kv_fp8.h) are tested against them byte for byte.
+KV_ROW = 64   # values of a cache row (csrc/kv_fp8.h KV_ROW)
+
+
+def kv_quantize(x: torch.Tensor):
+    """``x`` [..., 64] bf16 -> (``q`` uint8 [..., 64], ``scale`` fp32 [...]).  Per row: ``amax = max |x|``,
+    ``e = floor(log2(amax))`` (the exponent of amax as fp32) clamped to [-120, 127], 7 for a zero row;
+    ``scale = 2^(e - 7)``, a power of two (1.0 for a zero row); ``q = e4m3fn(x * 2^(7 - e))``, OCP
+    encoding, round to nearest even.  The product is exact in fp32 and the row's largest scaled
+    magnitude lies in [128, 256), so nothing reaches 448: no saturation and no NaN for finite input.
+    ``|kv_dequantize(q, scale) - x| <= amax / 16`` (half a step of e4m3 in [128, 256) is 8)."""
+    assert x.dtype == torch.bfloat16 and x.shape[-1] == KV_ROW, "kv_quantize takes bf16 rows of 64 values"
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    e = (torch.frexp(amax).exponent - 1).clamp(-120, 127)   # frexp: amax = m * 2^exp with m in [0.5, 1)
+    e = torch.where(amax == 0, torch.full_like(e, 7), e)
+    one = torch.ones_like(amax)
+    scale, inv = torch.ldexp(one, e - 7), torch.ldexp(one, 7 - e)
+    q = (xf * inv[..., None]).to(torch.float8_e4m3fn).view(torch.uint8)
+    return q, scale
+
+
+def kv_dequantize(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``float(q) * scale`` as bf16: exact, a 3-bit mantissa times a power of two."""
+    assert q.dtype == torch.uint8 and scale.dtype == torch.float32 and q.shape[:-1] == scale.shape
+    return (q.view(torch.float8_e4m3fn).float() * scale[..., None]).to(torch.bfloat16)
+
+
+def _is_fp8_cache(k_cache, v_cache, k_scale, v_scale) -> bool:
+    """uint8 caches with their scales select the FP8 paths; anything in between is a mistake."""
+    fp8 = k_cache.dtype == torch.uint8
+    if fp8:
+        assert v_cache.dtype == torch.uint8 and k_scale is not None and v_scale is not None, \
+            "FP8 caches are uint8 k / v plus k_scale and v_scale"
+        assert k_scale.shape == v_scale.shape == k_cache.shape[:3]
+        assert k_scale.dtype == v_scale.dtype == torch.float32
+    else:
+        assert k_scale is None and v_scale is None, "k_scale / v_scale go with uint8 (FP8) caches"
+    return fp8
+
+
+def kv_cache_fill(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor,
+                  v_scale: torch.Tensor, n: int, Sp: int):
+    """Prefill copy into one layer's FP8 cache: rows < ``n`` of every (sequence, head) of ``k_cache`` /
+    ``v_cache`` (uint8 [B, H, S_max, 64]) and ``k_scale`` / ``v_scale`` (fp32 [B, H, S_max]) receive
+    ``kv_quantize`` of the k / v columns of ``qkv`` [B * Sp, 3 * H * 64] bf16 (the training forward's
+    projection; row b * Sp + i is token i of sequence b).  Rows >= n are left alone.  GPU: one launch of
+    csrc/kv_quantize.hip; CPU tensors use the reference quantizer."""
+    B, H, S_max, Dh = k_cache.shape
+    assert _is_fp8_cache(k_cache, v_cache, k_scale, v_scale) and Dh == KV_ROW
+    assert qkv.dtype == torch.bfloat16 and qkv.shape == (B * Sp, 3 * H * Dh) and 0 <= n <= min(Sp, S_max)
+    if not _is_gpu(qkv):
+        q5 = qkv.view(B, Sp, 3, H, Dh)
+        for j, (cache, sc) in ((1, (k_cache, k_scale)), (2, (v_cache, v_scale))):
+            cache[:, :, :n], sc[:, :, :n] = kv_quantize(q5[:, :n, j].permute(0, 2, 1, 3))
+        return
+    for t in (qkv, k_cache, v_cache, k_scale, v_scale):
+        assert t.is_contiguous()
+    rc = _lib.lib().jdt_kv_quantize_rows(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), B, H,
+                                         Dh, S_max, Sp, n, _lib.stream_ptr())
+    _lib.check(rc, "jdt_kv_quantize_rows")
+
+
+def _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out, k_scale=None, v_scale=None):
+    """Composed torch path (any head dim / cache length, any device): reads ``pos`` on the host.  FP8
+    caches go through the reference quantizer: the token's rows are quantized and written, rows 0..p
+    dequantized, then the same math."""
     B, d3 = qkv.shape
+    fp8 = k_scale is not None
     if pos.numel() != 1:   # per row: every sequence as a batch of one at its own position
         for b in range(B):
-            _attention_decode_torch(qkv[b:b + 1], k_cache[b:b + 1], v_cache[b:b + 1], pos[b:b + 1], H, out[b:b + 1])
+            sc = (k_scale[b:b + 1], v_scale[b:b + 1]) if fp8 else (None, None)
+            _attention_decode_torch(qkv[b:b + 1], k_cache[b:b + 1], v_cache[b:b + 1], pos[b:b + 1], H, out[b:b + 1],
+                                    *sc)
         return out
     Dh = d3 // 3 // H
     S_max = k_cache.shape[2]
@@ -1053,9 +1124,15 @@ def _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out):
     if p < 0 or p >= S_max:
         return out
     q, k, v = qkv.view(B, 3, H, Dh).unbind(1)
-    k_cache[:, :, p] = k
-    v_cache[:, :, p] = v
-    Kc, Vc = _bf(k_cache[:, :, :p + 1].float()), _bf(v_cache[:, :, :p + 1].float())
+    if fp8:
+        k_cache[:, :, p], k_scale[:, :, p] = kv_quantize(k)
+        v_cache[:, :, p], v_scale[:, :, p] = kv_quantize(v)
+        Kc = kv_dequantize(k_cache[:, :, :p + 1], k_scale[:, :, :p + 1]).float()
+        Vc = kv_dequantize(v_cache[:, :, :p + 1], v_scale[:, :, :p + 1]).float()
+    else:
+        k_cache[:, :, p] = k
+        v_cache[:, :, p] = v
+        Kc, Vc = _bf(k_cache[:, :, :p + 1].float()), _bf(v_cache[:, :, :p + 1].float())
     s = torch.einsum("bhd,bhjd->bhj", _bf(q.float()), Kc) * (1.0 / (Dh ** 0.5))
     pr = torch.softmax(s, dim=-1).to(torch.bfloat16).float()   # p rounded to bf16 before P.V, as attention_fwd
     out.copy_(torch.einsum("bhj,bhjd->bhd", pr, Vc).reshape(B, H * Dh).to(torch.bfloat16))
@@ -1063,7 +1140,8 @@ def _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out):
 
 
 def attention_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, H: int,
-                     out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     out: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None,
+                     k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One query token per sequence against a KV cache.  ``qkv`` [B, 3*H*Dh] bf16 (the decode
     step's QKV projection, q | k | v as in training), ``k_cache`` / ``v_cache`` [B, H, S_max, Dh]
     bf16 (one layer), ``pos`` int32[1] (shared) or int32[B] (per row) -> o [B, H*Dh] bf16.
@@ -1075,17 +1153,45 @@ def attention_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     ``ws``, a combine folds them), which reads ``pos`` on the device like the first.  ``ws``: fp32
     scratch of >= ``attention_decode_ws_floats(B, H, S_max)`` words with any contents (``None``: a
     per-device buffer); the other paths ignore it.  Other GPU shapes run the composed torch path
-    (which syncs on ``pos``), as CPU tensors do."""
+    (which syncs on ``pos``), as CPU tensors do.
+
+    FP8 caches (``kv_quantize`` has the format): ``k_cache`` / ``v_cache`` uint8 [B, H, S_max, 64] with
+    ``k_scale`` / ``v_scale`` fp32 [B, H, S_max].  The token's k / v are quantized, row ``pos`` of the
+    caches and of the scales receives them, and attention sees every row -- the token's own included --
+    dequantized, as it will be read back later.  The same shape envelope, launches and workspace as
+    bf16 (the ``_fp8`` launchers of csrc/attn_decode.hip); the composed path uses the reference
+    quantizer."""
     B, d3 = qkv.shape
     d = d3 // 3
     Dh = d // H
     assert k_cache.shape == v_cache.shape and k_cache.shape[:2] == (B, H) and k_cache.shape[3] == Dh
+    fp8 = _is_fp8_cache(k_cache, v_cache, k_scale, v_scale)
     rows = _per_row(pos, B)
     S_max = k_cache.shape[2]
     if out is None:
         out = torch.zeros(B, d, dtype=torch.bfloat16, device=qkv.device)
     if not _is_gpu(qkv) or Dh != AD_HEAD_DIM or S_max > AD_LONG_MAX_ROWS:
-        return _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out)
+        return _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out, k_scale, v_scale)
+    if fp8:
+        for t in (qkv, k_cache, v_cache, k_scale, v_scale, out):
+            assert t.is_contiguous()
+        assert qkv.dtype == out.dtype == torch.bfloat16
+        scale = float(1.0 / (Dh ** 0.5))
+        if S_max <= AD_MAX_ROWS:
+            name = "jdt_attn_decode_fp8_rows" if rows else "jdt_attn_decode_fp8"
+            rc = getattr(_lib.lib(), name)(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
+                                           _ptr(out), _ptr(pos), B, H, Dh, S_max, scale, _lib.stream_ptr())
+            _lib.check(rc, name)
+            return out
+        if ws is None:
+            ws = _decode_workspace(qkv.device, attention_decode_ws_floats(B, H, S_max))
+        assert ws.is_contiguous() and ws.dtype == torch.float32 and ws.device == qkv.device
+        name = "jdt_attn_decode_fp8_long_rows" if rows else "jdt_attn_decode_fp8_long"
+        rc = getattr(_lib.lib(), name)(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
+                                       _ptr(out), _ptr(pos), _ptr(ws), ws.numel(), B, H, Dh, S_max, scale,
+                                       _lib.stream_ptr())
+        _lib.check(rc, name)
+        return out
     for t in (qkv, k_cache, v_cache, out):
         assert t.is_contiguous() and t.dtype == torch.bfloat16
     if S_max <= AD_MAX_ROWS:
@@ -1174,16 +1280,24 @@ def _append_host_ranges(pos, count, B, C, S_max, rows):
     return [(b, p, n) for b, (p, n) in enumerate(zip(pv, nv)) if 0 < n <= C and 0 <= p <= S_max - n]
 
 
-def _attention_append_torch(qkv, k_cache, v_cache, pos, H, C, count, rows, out):
-    """Composed torch path (any head dim / cache length, any device): reads ``pos`` on the host."""
+def _attention_append_torch(qkv, k_cache, v_cache, pos, H, C, count, rows, out, k_scale=None, v_scale=None):
+    """Composed torch path (any head dim / cache length, any device): reads ``pos`` on the host.  FP8
+    caches go through the reference quantizer: the new rows are quantized and written, rows 0..p+n-1
+    dequantized, then the same math."""
     B, _, S_max, Dh = k_cache.shape
     d = H * Dh
     q5, o3 = qkv.view(B, C, 3, H, Dh), out.view(B, C, d)
     for b, p, n in _append_host_ranges(pos, count, B, C, S_max, rows):
         q, k, v = q5[b, :n].unbind(1)   # [n, H, Dh]
-        k_cache[b, :, p:p + n] = k.permute(1, 0, 2)
-        v_cache[b, :, p:p + n] = v.permute(1, 0, 2)
-        Kc, Vc = _bf(k_cache[b, :, :p + n].float()), _bf(v_cache[b, :, :p + n].float())
+        if k_scale is not None:
+            k_cache[b, :, p:p + n], k_scale[b, :, p:p + n] = kv_quantize(k.permute(1, 0, 2))
+            v_cache[b, :, p:p + n], v_scale[b, :, p:p + n] = kv_quantize(v.permute(1, 0, 2))
+            Kc = kv_dequantize(k_cache[b, :, :p + n], k_scale[b, :, :p + n]).float()
+            Vc = kv_dequantize(v_cache[b, :, :p + n], v_scale[b, :, :p + n]).float()
+        else:
+            k_cache[b, :, p:p + n] = k.permute(1, 0, 2)
+            v_cache[b, :, p:p + n] = v.permute(1, 0, 2)
+            Kc, Vc = _bf(k_cache[b, :, :p + n].float()), _bf(v_cache[b, :, :p + n].float())
         s = torch.einsum("ihd,hjd->hij", _bf(q.float()), Kc) * (1.0 / (Dh ** 0.5))
         key, qabs = torch.arange(p + n, device=s.device), p + torch.arange(n, device=s.device)
         s = s.masked_fill(key[None, :] > qabs[:, None], float("-inf"))
@@ -1194,7 +1308,8 @@ def _attention_append_torch(qkv, k_cache, v_cache, pos, H, C, count, rows, out):
 
 def attention_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, H: int,
                      C: int, count: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                     ws: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     ws: Optional[torch.Tensor] = None, k_scale: Optional[torch.Tensor] = None,
+                     v_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``C`` new query tokens per sequence against a KV cache (chunked prefill, teacher forcing,
     scoring a continuation).  ``qkv`` [B*C, 3*H*Dh] bf16 (row b*C + i is token i of sequence b;
     q | k | v as in training), ``k_cache`` / ``v_cache`` [B, H, S_max, Dh] bf16 (one layer), ``pos``
@@ -1217,7 +1332,13 @@ def attention_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     increasing order -- for a few new rows against a deep cache, where the one launch is a handful of
     workgroups that each walk the whole cache.  The caches come out bit for bit as from the one
     launch, so do the rows with ``p + i < 512``; deeper rows differ in rounding only, and their bits
-    still depend on (q_t, K[0..t], V[0..t]) alone.  The composed torch path ignores ``ws``."""
+    still depend on (q_t, K[0..t], V[0..t]) alone.  The composed torch path ignores ``ws``.
+
+    FP8 caches (``kv_quantize`` has the format): uint8 ``k_cache`` / ``v_cache`` with ``k_scale`` /
+    ``v_scale`` fp32 [B, H, S_max].  Cache rows p..p+n-1 and their scales receive ``kv_quantize`` of the
+    tokens' k / v, and every key a query sees -- those of its own chunk included -- is the dequantized
+    row, so the cut invariance above survives.  Dequantization is exact, so ``o`` has the bits of the bf16
+    kernel on the dequantized values.  One launch only: FP8 with ``ws`` is refused."""
     T, d3 = qkv.shape
     d = d3 // 3
     Dh = d // H
@@ -1229,8 +1350,26 @@ def attention_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     if out is None:
         out = torch.zeros(T, d, dtype=torch.bfloat16, device=qkv.device)
     assert out.shape == (T, d)
+    fp8 = _is_fp8_cache(k_cache, v_cache, k_scale, v_scale)
+    if fp8 and ws is not None:
+        raise ValueError("split append (ws) does not take FP8 caches")
     if not _is_gpu(qkv) or Dh != AD_HEAD_DIM or S_max > AP_MAX_ROWS or C > AP_MAX_CHUNK:
-        return _attention_append_torch(qkv, k_cache, v_cache, pos, H, C, count, rows, out)
+        return _attention_append_torch(qkv, k_cache, v_cache, pos, H, C, count, rows, out, k_scale, v_scale)
+    if fp8:
+        for t in (qkv, k_cache, v_cache, k_scale, v_scale, out):
+            assert t.is_contiguous()
+        assert qkv.dtype == out.dtype == torch.bfloat16
+        scale = float(1.0 / (Dh ** 0.5))
+        if rows:
+            rc = _lib.lib().jdt_attn_append_fp8_rows(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale),
+                                                     _ptr(v_scale), _ptr(out), _ptr(pos), _ptr(count), B, C, H, Dh,
+                                                     S_max, scale, _lib.stream_ptr())
+            _lib.check(rc, "jdt_attn_append_fp8_rows")
+        else:
+            rc = _lib.lib().jdt_attn_append_fp8(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
+                                                _ptr(out), _ptr(pos), B, C, H, Dh, S_max, scale, _lib.stream_ptr())
+            _lib.check(rc, "jdt_attn_append_fp8")
+        return out
     for t in (qkv, k_cache, v_cache, out):
         assert t.is_contiguous() and t.dtype == torch.bfloat16
     scale = float(1.0 / (Dh ** 0.5))

@@ -65,6 +65,23 @@ int jdt_embed_append(const int* tokens, const void* wte, const void* wpe, void* 
                      int S_max, int d, int vocab, void* stream);
 int jdt_embed_append_rows(const int* tokens, const void* wte, const void* wpe, void* out, const int* pos,
                           const int* count, int B, int C, int S_max, int d, int vocab, void* stream);
+int jdt_attn_decode_fp8(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale, void* o,
+                        const int* pos, int B, int H, int Dh, int S_max, float scale, void* stream);
+int jdt_attn_decode_fp8_rows(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale, void* o,
+                             const int* pos, int B, int H, int Dh, int S_max, float scale, void* stream);
+int jdt_attn_decode_fp8_long(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale, void* o,
+                             const int* pos, float* ws, long ws_floats, int B, int H, int Dh, int S_max, float scale,
+                             void* stream);
+int jdt_attn_decode_fp8_long_rows(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
+                                  void* o, const int* pos, float* ws, long ws_floats, int B, int H, int Dh, int S_max,
+                                  float scale, void* stream);
+int jdt_attn_append_fp8(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale, void* o,
+                        const int* pos, int B, int C, int H, int Dh, int S_max, float scale, void* stream);
+int jdt_attn_append_fp8_rows(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale, void* o,
+                             const int* pos, const int* count, int B, int C, int H, int Dh, int S_max, float scale,
+                             void* stream);
+int jdt_kv_quantize_rows(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale, int B, int H,
+                         int Dh, int S_max, int Sp, int n, void* stream);
 }
 
 static int failures = 0;
@@ -280,6 +297,63 @@ int main() {
          "embed_append_rows rejects C 1025");
   EXPECT(jdt_embed_append_rows(ip, buf, buf, buf, ip, ip, 0, 64, 128, 64, 8, nullptr) == 0,
          "embed_append_rows B = 0 is a no-op");
+  // FP8 KV cache launchers: the bf16 envelopes, null scales, 8-byte caches and 4-byte scales
+  float* sp = reinterpret_cast<float*>(buf);
+  float* sp_mis = reinterpret_cast<float*>(buf + 2);
+  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, sp, sp, buf, ip, 1, 2, 32, 128, .125f, nullptr) == -3,
+         "attn_decode_fp8 rejects head dim 32");
+  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, sp, sp, buf, ip, 1, 2, 64, 129, .125f, nullptr) == -4,
+         "attn_decode_fp8 rejects S_max > 128");
+  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, nullptr, sp, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -2,
+         "attn_decode_fp8 rejects a null k_scale");
+  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, sp, nullptr, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -2,
+         "attn_decode_fp8 rejects a null v_scale");
+  EXPECT(jdt_attn_decode_fp8(buf, buf + 4, buf, sp, sp, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -6,
+         "attn_decode_fp8 rejects a cache off an 8-byte boundary");
+  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, sp, sp_mis, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -6,
+         "attn_decode_fp8 rejects a misaligned scale");
+  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, sp, sp, buf, ip, 0, 2, 64, 128, .125f, nullptr) == 0,
+         "attn_decode_fp8 B = 0 is a no-op");
+  EXPECT(jdt_attn_decode_fp8_rows(buf, buf, buf, sp, sp, buf, nullptr, 1, 2, 64, 128, .125f, nullptr) == -2,
+         "attn_decode_fp8_rows rejects null");
+  EXPECT(jdt_attn_decode_fp8_rows(buf, buf, buf, sp, sp, buf, ip, 0, 2, 64, 128, .125f, nullptr) == 0,
+         "attn_decode_fp8_rows B = 0 is a no-op");
+  EXPECT(jdt_attn_decode_fp8_long(buf, buf, buf, sp, sp, buf, ip, fp, 1L << 30, 1, 2, 64, 32769, .125f, nullptr) == -4,
+         "attn_decode_fp8_long rejects S_max > 32768");
+  EXPECT(jdt_attn_decode_fp8_long(buf, buf, buf, sp, nullptr, buf, ip, fp, 396, 1, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_decode_fp8_long rejects a null v_scale");
+  EXPECT(jdt_attn_decode_fp8_long(buf, buf, buf, sp, sp, buf, ip, fp, 395, 1, 2, 64, 320, .125f, nullptr) == -10,
+         "attn_decode_fp8_long rejects a short ws");
+  EXPECT(jdt_attn_decode_fp8_long(buf, buf, buf, sp, sp, buf, ip, fp, 0, 0, 2, 64, 320, .125f, nullptr) == 0,
+         "attn_decode_fp8_long B = 0 is a no-op");
+  EXPECT(jdt_attn_decode_fp8_long_rows(buf, buf, buf + 4, sp, sp, buf, ip, fp, 396, 1, 2, 64, 320, .125f, nullptr) == -6,
+         "attn_decode_fp8_long_rows rejects a cache off an 8-byte boundary");
+  EXPECT(jdt_attn_decode_fp8_long_rows(buf, buf, buf, sp, sp, buf, ip, fp, 395, 1, 2, 64, 320, .125f, nullptr) == -10,
+         "attn_decode_fp8_long_rows rejects a short ws");
+  EXPECT(jdt_attn_append_fp8(buf, buf, buf, sp, sp, buf, ip, 1, 64, 2, 32, 320, .125f, nullptr) == -3,
+         "attn_append_fp8 rejects head dim 32");
+  EXPECT(jdt_attn_append_fp8(buf, buf, buf, sp, sp, buf, ip, 1, 1025, 2, 64, 320, .125f, nullptr) == -11,
+         "attn_append_fp8 rejects C 1025");
+  EXPECT(jdt_attn_append_fp8(buf, buf, buf, nullptr, sp, buf, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_append_fp8 rejects a null k_scale");
+  EXPECT(jdt_attn_append_fp8(buf, buf + 4, buf, sp, sp, buf, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
+         "attn_append_fp8 rejects a cache off an 8-byte boundary");
+  EXPECT(jdt_attn_append_fp8(buf, buf, buf, sp, sp, buf, ip, 0, 64, 2, 64, 320, .125f, nullptr) == 0,
+         "attn_append_fp8 B = 0 is a no-op");
+  EXPECT(jdt_attn_append_fp8_rows(buf, buf, buf, sp, sp, buf, ip, nullptr, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
+         "attn_append_fp8_rows rejects a null count");
+  EXPECT(jdt_attn_append_fp8_rows(buf, buf, buf, sp, sp_mis, buf, ip, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
+         "attn_append_fp8_rows rejects a misaligned scale");
+  EXPECT(jdt_kv_quantize_rows(buf, buf, buf, sp, sp, 1, 2, 32, 128, 128, 16, nullptr) == -3,
+         "kv_quantize_rows rejects head dim 32");
+  EXPECT(jdt_kv_quantize_rows(buf, buf, buf, sp, sp, 1, 2, 64, 128, 64, 65, nullptr) == -5,
+         "kv_quantize_rows rejects n > Sp");
+  EXPECT(jdt_kv_quantize_rows(buf, buf, buf, sp, nullptr, 1, 2, 64, 128, 128, 16, nullptr) == -2,
+         "kv_quantize_rows rejects null");
+  EXPECT(jdt_kv_quantize_rows(buf, buf + 4, buf, sp, sp, 1, 2, 64, 128, 128, 16, nullptr) == -6,
+         "kv_quantize_rows rejects a cache off an 8-byte boundary");
+  EXPECT(jdt_kv_quantize_rows(buf, buf, buf, sp, sp, 1, 2, 64, 128, 128, 0, nullptr) == 0,
+         "kv_quantize_rows n = 0 is a no-op");
   std::printf("asan host check: %d failure(s)\n", failures);
   return failures ? 1 : 0;
 }

@@ -4,7 +4,7 @@ eagerly against one captured step replayed per token, plus the kernel-launcher c
 
     python tools/bench_generate.py [--steps 100] [--temperature 0.0] [--ragged] [--seq-len N] [--prompt-len P]
                                    [--prefill-chunk N[,N...]] [--split-append] [--beams W[,W...]]
-                                   [--speculative K[,K...]]
+                                   [--speculative K[,K...]] [--kv-dtype bf16,fp8]
 
 Each figure: ``--steps`` decode steps after a 16-token prefill, timed with events around the
 whole loop (prefill excluded), median of 5 runs.  ``--seq-len N`` > 128 builds the LM with an
@@ -24,7 +24,9 @@ adds, per batch size and draft count K, the captured speculative round of ``Gene
 the plain captured step of the main line: us per round, tokens per round and hence us per token, for the
 target itself as the draft (acceptance near 1: the ceiling on tokens per round, at the full cost of K + 1
 target-sized draft steps) and for a 1-layer draft with fresh weights (acceptance near 0: one token per
-round, the worst case) (``spec_lines``).
+round, the worst case) (``spec_lines``).  ``--kv-dtype bf16,fp8`` prints the main line once per cache dtype
+(``Generator(..., kv_dtype=)``), each with the bytes its K / V caches and their scales hold; the extra
+lines above are bf16-only and follow the bf16 line.
 """
 import argparse
 import os
@@ -237,7 +239,10 @@ def main():
     ap.add_argument("--seq-len", type=int, default=128, help="cache rows; > 128: the prompt is seq_len - steps - 1")
     ap.add_argument("--prompt-len", type=int, default=None, help="override the prompt length")
     ap.add_argument("--batch", default="1,16", help="comma-separated batch sizes of the main lines")
+    ap.add_argument("--kv-dtype", default="bf16", metavar="bf16[,fp8]",
+                    help="comma-separated KV cache dtypes: the main line once per dtype, with the cache's bytes")
     a = ap.parse_args()
+    dtypes = a.kv_dtype.split(",")
     dev = torch.device("cuda", 0)
     cfg = TransformerConfig(seq_len=a.seq_len)
     global PROMPT
@@ -248,8 +253,8 @@ def main():
     assert PROMPT >= 1 and PROMPT + a.steps <= cfg.seq_len
     model = TransformerLM(cfg)
     P = FlatParams(model.param_specs(), device=dev).init_(0)
-    for B in (int(v) for v in a.batch.split(",")):
-        gen = Generator(model, P, B, dev)
+    for B, kv_dtype in ((int(v), t) for v in a.batch.split(",") for t in dtypes):
+        gen = Generator(model, P, B, dev, kv_dtype=kv_dtype)
         prompt = torch.randint(0, cfg.vocab_size, (B, PROMPT), generator=torch.Generator().manual_seed(1))
         prompt = prompt.to(torch.int32).to(dev)
         gen.generate(prompt, 2, temperature=a.temperature, capture=True)   # warm-up + the step capture
@@ -259,14 +264,17 @@ def main():
         calls = launches_per_step(gen)
         t_e = timed(gen.step, reset, a.steps)
         depth = f" S={a.seq_len} P={PROMPT}" if a.seq_len != 128 or a.prompt_len is not None else ""
-        line = (f"generate B={B:2d} T={a.temperature}{depth}: eager {t_e:7.1f} us/step "
+        line = (f"generate B={B:2d} T={a.temperature}{depth} kv={kv_dtype:>4}: eager {t_e:7.1f} us/step "
                 f"({B / t_e * 1e6:9.0f} tokens/s)")
         t_g = float("nan")
         if graph is not None:
             t_g = timed(graph.replay, reset, a.steps)
             line += f" | captured {t_g:7.1f} us/step ({B / t_g * 1e6:9.0f} tokens/s)"
-        print(line + f" | {sum(calls.values())} launcher calls/step: "
+        print(line + f" | cache {gen.kv.cache_bytes() / 2 ** 20:8.2f} MiB | {sum(calls.values())} launcher calls/step: "
               + ", ".join(f"{k[4:]} x{v}" for k, v in sorted(calls.items())), flush=True)
+        if kv_dtype != "bf16":   # the extra lines below run on bf16 caches
+            del gen, graph, reset
+            continue
         if a.speculative:
             spec_lines(model, P, B, dev, [int(v) for v in a.speculative.split(",")], a.steps, a.temperature, depth, t_g)
         if a.prefill_chunk:
