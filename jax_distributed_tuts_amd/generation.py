@@ -400,12 +400,8 @@ class Generator:
         if x is None:   # once per chunk size, zero-initialised: rows past a count stay finite
             x = self._chunk_bufs[chunk] = torch.zeros(B * chunk, c.d_model, dtype=torch.bfloat16, device=self.device)
         last = torch.zeros(B, c.d_model, dtype=torch.bfloat16, device=self.device) if logits else None
-        if self.split_append and max(nb) > 0:
-            # the largest slice's partials; an outgrown buffer is replaced, a larger one is kept
-            need = K.attention_append_ws_floats(B, c.n_heads, min(chunk, max(nb)), c.seq_len)
-            if kv.append_ws is None or kv.append_ws.numel() < need:
-                kv.append_ws = torch.empty(need, dtype=torch.float32, device=self.device)
-                self._drop_spec_graphs()
+        if max(nb) > 0:
+            self._ensure_append_ws(min(chunk, max(nb)))   # the largest slice's partials
         for lo in range(0, max(nb), chunk):
             C = min(chunk, max(nb) - lo)
             cnt = [min(max(v - lo, 0), C) for v in nb]
@@ -427,6 +423,17 @@ class Generator:
             self.logits = self.model.lm_head(P, last)
             return self.logits
         return None
+
+    def _ensure_append_ws(self, C: int):
+        """With ``split_append``: ``kv.append_ws`` holds the partials of an append slice of ``C`` rows.  An
+        outgrown buffer is replaced, a larger one is kept."""
+        if not self.split_append:
+            return
+        kv, c = self.kv, self.model.cfg
+        need = K.attention_append_ws_floats(self.batch, c.n_heads, C, c.seq_len)
+        if kv.append_ws is None or kv.append_ws.numel() < need:
+            kv.append_ws = torch.empty(need, dtype=torch.float32, device=self.device)
+            self._drop_spec_graphs()
 
     def extend(self, tokens: torch.Tensor, lens: Optional[torch.Tensor] = None, *, chunk: int = 64,
                logits: bool = False) -> Optional[torch.Tensor]:
@@ -528,8 +535,7 @@ class Generator:
     def _spec_state(self, k: int) -> SpecState:
         """The checks common to ``spec_step`` / ``verify`` and the state of rounds of ``k`` drafts (made
         on first use, with the round's workspaces, so that nothing is allocated under a capture)."""
-        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= K.SPEC_MAX_DRAFTS:
-            raise ValueError(f"speculative k must be an int in 1..{K.SPEC_MAX_DRAFTS}, got {k!r}")
+        self._check_spec_k(k, "speculative k")
         if not self._live:
             raise ValueError("speculative decoding needs a live cache: call prefill (or generate) first")
         if not self.kv.per_row:
@@ -540,12 +546,13 @@ class Generator:
         c, C = self.model.cfg, k + 1
         if C not in self._chunk_bufs:
             self._chunk_bufs[C] = torch.zeros(self.batch * C, c.d_model, dtype=torch.bfloat16, device=self.device)
-        if self.split_append:
-            need = K.attention_append_ws_floats(self.batch, c.n_heads, C, c.seq_len)
-            if self.kv.append_ws is None or self.kv.append_ws.numel() < need:
-                self.kv.append_ws = torch.empty(need, dtype=torch.float32, device=self.device)
-                self._drop_spec_graphs()
+        self._ensure_append_ws(C)
         return st
+
+    @staticmethod
+    def _check_spec_k(k, what: str):
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= K.SPEC_MAX_DRAFTS:
+            raise ValueError(f"{what} must be an int in 1..{K.SPEC_MAX_DRAFTS}, got {k!r}")
 
     def _drop_spec_graphs(self):
         """A captured round holds ``kv.append_ws``' pointer: a replaced buffer retires those graphs."""
@@ -611,20 +618,37 @@ class Generator:
         d.step(sample=False)
         return self._verify(st, d.kv.pos_rows, d.kv.end)
 
-    def _generate_spec(self, prompt, max_new_tokens, k, graph, prompt_lens, pad_id, prefill_chunk):
-        c, kv, d = self.model.cfg, self.kv, self.draft
-        if d is None:
-            raise ValueError("speculative decoding needs a draft model: Generator(..., draft=(model, P))")
-        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= K.SPEC_MAX_DRAFTS:
-            raise ValueError(f"speculative must be an int in 1..{K.SPEC_MAX_DRAFTS}, got {k!r}")
-        Pn = prompt.shape[1] if prompt.dim() == 2 else 0
+    def _ragged_begin(self, prompt, prompt_lens, max_new_tokens, eos_id):
+        """What a per-row generation checks before its prefill -> (lens, longest): ``self.eos_id`` (set from
+        ``eos_id``) is a token, ``lens`` is ``prompt_lens`` or the prompt's width for every row, and the longest
+        row can still grow by ``max_new_tokens``."""
+        c = self.model.cfg
+        if self.eos_id >= c.vocab_size or (eos_id is not None and self.eos_id < 0):
+            raise ValueError(f"eos_id {eos_id} outside [0, {c.vocab_size})")
         if prompt_lens is None:
+            Pn = prompt.shape[1] if prompt.dim() == 2 else 0
             prompt_lens = torch.full((self.batch,), Pn, dtype=torch.int32)
         lens = torch.as_tensor(prompt_lens)
         longest = int(lens.max()) if lens.numel() else 0
         if max_new_tokens < 0 or longest + max_new_tokens > c.seq_len:
             raise ValueError(f"longest prompt {longest} + max_new_tokens {max_new_tokens} exceeds seq_len "
                              f"{c.seq_len} (the learned positions end there)")
+        return lens, longest
+
+    def _ragged_end(self, width: int, pad_id: int) -> torch.Tensor:
+        """The return value of a per-row generation: sets ``lengths`` and copies the first ``width`` columns of
+        ``tokens`` with ``pad_id`` at and past each row's length."""
+        self.lengths = self.kv.pos_rows + 1
+        out = self.kv.tokens[:, :width].clone()
+        out[torch.arange(out.shape[1], device=self.device)[None] >= self.lengths[:, None]] = pad_id
+        return out
+
+    def _generate_spec(self, prompt, max_new_tokens, k, graph, prompt_lens, eos_id, pad_id, prefill_chunk):
+        c, kv, d = self.model.cfg, self.kv, self.draft
+        if d is None:
+            raise ValueError("speculative decoding needs a draft model: Generator(..., draft=(model, P))")
+        self._check_spec_k(k, "speculative")
+        lens, longest = self._ragged_begin(prompt, prompt_lens, max_new_tokens, eos_id)
         self.prefill(prompt, lens, chunk=prefill_chunk)
         d.prefill(prompt, lens, chunk=prefill_chunk)   # the same tokens into the shared tensor again
         kv.end.copy_(kv.pos_rows + 1 + max_new_tokens)
@@ -647,10 +671,7 @@ class Generator:
                 break
         self.spec_drafted, self.spec_accepted, self.spec_emitted = (t.clone() for t in (st.drafted, st.accepted,
                                                                                          st.emitted))
-        self.lengths = kv.pos_rows + 1
-        out = kv.tokens[:, :longest + max_new_tokens].clone()
-        out[torch.arange(out.shape[1], device=self.device)[None] >= self.lengths[:, None]] = pad_id
-        return out
+        return self._ragged_end(longest + max_new_tokens, pad_id)
 
     # ------------------------------------------------------------------ generate
     def generate(self, prompt: torch.Tensor, max_new_tokens: int, temperature: float = 0.0, seed: int = 0,
@@ -689,9 +710,8 @@ class Generator:
         graph = capture and self.device.type == "cuda"
         run = self._replay if graph else self.step
         if speculative is not None:
-            if self.eos_id >= c.vocab_size or (eos_id is not None and self.eos_id < 0):
-                raise ValueError(f"eos_id {eos_id} outside [0, {c.vocab_size})")
-            return self._generate_spec(prompt, max_new_tokens, speculative, graph, prompt_lens, pad_id, prefill_chunk)
+            return self._generate_spec(prompt, max_new_tokens, speculative, graph, prompt_lens, eos_id, pad_id,
+                                       prefill_chunk)
         if prompt_lens is None and eos_id is None:
             if max_new_tokens < 0 or Pn + max_new_tokens > c.seq_len:
                 raise ValueError(f"prompt length {Pn} + max_new_tokens {max_new_tokens} exceeds seq_len "
@@ -701,15 +721,7 @@ class Generator:
                 run()
             self.lengths = torch.full((self.batch,), Pn + max_new_tokens, dtype=torch.int32, device=self.device)
             return self.kv.tokens[:, :Pn + max_new_tokens].clone()
-        if self.eos_id >= c.vocab_size or (eos_id is not None and self.eos_id < 0):
-            raise ValueError(f"eos_id {eos_id} outside [0, {c.vocab_size})")
-        if prompt_lens is None:
-            prompt_lens = torch.full((self.batch,), Pn, dtype=torch.int32)
-        lens = torch.as_tensor(prompt_lens)
-        longest = int(lens.max()) if lens.numel() else 0
-        if max_new_tokens < 0 or longest + max_new_tokens > c.seq_len:
-            raise ValueError(f"longest prompt {longest} + max_new_tokens {max_new_tokens} exceeds seq_len "
-                             f"{c.seq_len} (the learned positions end there)")
+        lens, longest = self._ragged_begin(prompt, prompt_lens, max_new_tokens, eos_id)
         self.prefill(prompt, lens, chunk=prefill_chunk)
         kv = self.kv
         kv.end.copy_(kv.pos_rows + 1 + max_new_tokens)
@@ -718,10 +730,7 @@ class Generator:
             # a host read serialises the replay loop: look only every 16 steps
             if self.eos_id >= 0 and i % 16 == 0 and i < max_new_tokens and bool((kv.pos_rows + 1 >= kv.end).all()):
                 break
-        self.lengths = kv.pos_rows + 1
-        out = kv.tokens[:, :longest + max_new_tokens].clone()
-        out[torch.arange(out.shape[1], device=self.device)[None] >= self.lengths[:, None]] = pad_id
-        return out
+        return self._ragged_end(longest + max_new_tokens, pad_id)
 
     # ------------------------------------------------------------------ beam search
     def beam_begin(self, prompt: torch.Tensor, num_beams: int, eos_id: Optional[int] = None,

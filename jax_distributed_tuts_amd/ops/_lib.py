@@ -9,6 +9,7 @@ gloo simulation mode and as the numerics oracle in tests).
 from __future__ import annotations
 
 import ctypes
+import itertools
 import os
 import threading
 from ctypes import c_float, c_int, c_long, c_ulonglong, c_void_p
@@ -114,55 +115,15 @@ _SIGS = {
     "jdt_flash_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "jdt_flash_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                               c_int, c_int, c_float, c_int, c_void_p]),
-    # csrc/attn_decode.hip: (qkv, k_cache, v_cache, o, pos, B, H, Dh, S_max, scale, stream)
-    "jdt_attn_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                c_float, c_void_p]),
-    # (tokens, wte, wpe, out, pos, B, S_max, d, vocab, stream)
+    # csrc/attn_decode.hip: (tokens, wte, wpe, out, pos, B, S_max, d, vocab, stream)
     "jdt_embed_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                  c_void_p]),
     # (logits, ld, B, V, temperature, seed, stream_id, tokens, S_max, pos, ticket, stream)
     "jdt_sample": (c_int, [c_void_p, c_long, c_int, c_int, c_float, c_ulonglong, ctypes.c_uint, c_void_p, c_int,
                            c_void_p, c_void_p, c_void_p]),
-    # per-row positions (pos int32[B]): the signatures of jdt_attn_decode / jdt_embed_decode
-    "jdt_attn_decode_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                     c_float, c_void_p]),
+    # per-row positions (pos int32[B]): the signature of jdt_embed_decode
     "jdt_embed_decode_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                       c_void_p]),
-    # split-KV decode attention (S_max <= 32768), shared / per-row positions:
-    # (qkv, k_cache, v_cache, o, pos, ws, ws_floats, B, H, Dh, S_max, scale, stream)
-    "jdt_attn_decode_long": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int,
-                                     c_int, c_int, c_float, c_void_p]),
-    "jdt_attn_decode_long_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int,
-                                          c_int, c_int, c_int, c_float, c_void_p]),
-    # csrc/attn_append.hip, C new tokens per sequence: (qkv, k_cache, v_cache, o, pos, B, C, H, Dh, S_max, scale,
-    # stream); per row: (..., pos, count, B, ...)
-    "jdt_attn_append": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                c_float, c_void_p]),
-    "jdt_attn_append_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                     c_int, c_int, c_float, c_void_p]),
-    # the split-KV pair of launches: (qkv, k_cache, v_cache, o, pos, ws, ws_floats, B, C, H, Dh, S_max, scale,
-    # stream); per row: (..., pos, count, ws, ...)
-    "jdt_attn_append_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int,
-                                      c_int, c_int, c_int, c_float, c_void_p]),
-    "jdt_attn_append_split_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                           c_long, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    # FP8 KV cache (csrc/kv_fp8.h): the bf16 launchers' lists with k_scale, v_scale after the caches
-    # (qkv, k_cache, v_cache, k_scale, v_scale, o, pos, B, H, Dh, S_max, scale, stream)
-    "jdt_attn_decode_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                    c_int, c_int, c_int, c_float, c_void_p]),
-    "jdt_attn_decode_fp8_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                         c_int, c_int, c_int, c_float, c_void_p]),
-    # (qkv, k_cache, v_cache, k_scale, v_scale, o, pos, ws, ws_floats, B, H, Dh, S_max, scale, stream)
-    "jdt_attn_decode_fp8_long": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_long, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "jdt_attn_decode_fp8_long_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                              c_void_p, c_long, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    # (qkv, k_cache, v_cache, k_scale, v_scale, o, pos, B, C, H, Dh, S_max, scale, stream); per row: (..., pos,
-    # count, B, ...)
-    "jdt_attn_append_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                    c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "jdt_attn_append_fp8_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     # csrc/kv_quantize.hip: (qkv, k_cache, v_cache, k_scale, v_scale, B, H, Dh, S_max, Sp, n, stream)
     "jdt_kv_quantize_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                      c_int, c_int, c_void_p]),
@@ -196,6 +157,26 @@ _SIGS = {
     "jdt_spec_commit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
+
+
+# The KV-cache attention launchers (csrc/attn_decode.hip, csrc/attn_append.hip) are one family: a variant is
+# (append, fp8, split, rows) and its name and argument list follow from those four, here and where
+# ops/kernels.py builds the call.  FP8 caches bring their scales, per-row append its counts, the split pair of
+# launches (decode: ``_long``) its workspace, append the chunk size C:
+# (qkv, k_cache, v_cache, [k_scale, v_scale,] o, pos, [count,] [ws, ws_floats,] B, [C,] H, Dh, S_max, scale, stream)
+def _kv_attn_name(append: bool, fp8: bool, split: bool, rows: bool) -> str:
+    split_tag = "_split" if append else "_long"
+    return ("jdt_attn_append" if append else "jdt_attn_decode") + "_fp8" * fp8 + split_tag * split + "_rows" * rows
+
+
+def _kv_attn_argtypes(append: bool, fp8: bool, split: bool, rows: bool) -> list:
+    pointers = 5 + 2 * fp8 + (append and rows)
+    return [c_void_p] * pointers + [c_void_p, c_long] * split + [c_int] * (4 + append) + [c_float, c_void_p]
+
+
+for _v in itertools.product((False, True), repeat=4):
+    if not (_v[0] and _v[1] and _v[2]):   # no split append on FP8 caches
+        _SIGS[_kv_attn_name(*_v)] = (c_int, _kv_attn_argtypes(*_v))
 
 
 def _declare(lib):

@@ -307,116 +307,86 @@ __global__ void __launch_bounds__(1024) attn_append_combine_kernel(const float* 
 }  // namespace jdt
 using namespace jdt;
 
-// Everything is checked before anything is launched.  -11: C outside 1..1024; -5: a batch or
-// head count the grid cannot hold (B * H is the grid's y extent).
-template <bool ROWS>
-static int attn_append_launch(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, const int* count,
-                              int B, int C, int H, int Dh, int S_max, float scale, void* stream) {
-  if (Dh != AT_D) return -3;
-  if (S_max < 1 || S_max > AP_SMAX) return -4;
-  if (C < 1 || C > AP_CMAX) return -11;
-  if (B < 0 || H < 1 || (long)B * H > 65535) return -5;
-  if (!qkv || !k_cache || !v_cache || !o || !pos || (ROWS && !count)) return -2;
-  if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
-  if (B == 0) return 0;
-  hipLaunchKernelGGL((attn_append_kernel<ROWS, false, false>), dim3((C + AT_T - 1) / AT_T, B * H), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(k_cache),
-                     static_cast<bf16_t*>(v_cache), static_cast<bf16_t*>(o), pos, count, C, H, S_max, scale,
-                     static_cast<float*>(nullptr), static_cast<float*>(nullptr));
-  return HIP_LAUNCH_CHECK();
+#include "kv_launch.h"
+
+// One instantiation's launch: attn_append_kernel<ROWS, SPLIT, FP8>, grid (query tiles, B * H) and, SPLIT, one
+// more extent of 512-key spans with the workspace in the place of o, then the combine on the same stream.
+template <bool ROWS, bool SPLIT, bool FP8>
+static int attn_append_launch(const KvAttnArgs& a, hipStream_t stream) {
+  using cache_t = std::conditional_t<FP8, uint8_t, bf16_t>;
+  using out_t = std::conditional_t<SPLIT, float, bf16_t>;
+  const int n_qt = (a.C + AT_T - 1) / AT_T, n_spans = SPLIT ? (a.S_max + AP_SPAN - 1) / AP_SPAN : 1;
+  hipLaunchKernelGGL((attn_append_kernel<ROWS, SPLIT, FP8>), dim3(n_qt, a.B * a.H, n_spans), dim3(256), 0, stream,
+                     static_cast<const bf16_t*>(a.qkv), static_cast<cache_t*>(a.k_cache),
+                     static_cast<cache_t*>(a.v_cache), static_cast<out_t*>(SPLIT ? a.ws : a.o), a.pos, a.count, a.C,
+                     a.H, a.S_max, a.scale, a.k_scale, a.v_scale);
+  int rc = HIP_LAUNCH_CHECK();
+  if constexpr (SPLIT) {
+    if (rc) return rc;
+    hipLaunchKernelGGL(attn_append_combine_kernel<ROWS>, dim3(n_qt, a.B * a.H), dim3(1024), 0, stream,
+                       static_cast<const float*>(a.ws), static_cast<bf16_t*>(a.o), a.pos, a.count, a.C, a.H, a.S_max,
+                       n_spans);
+    rc = HIP_LAUNCH_CHECK();
+  }
+  return rc;
+}
+
+// The six append entry points: kv_attn_check's ladder (B * H is the grid's y extent; split: a workspace of
+// B * H * ceil(C / 64) * ceil(S_max / 512) * 64 * 66 floats), then the instantiation the flags name.  No entry
+// point sets split with fp8 (the kernel has no such instantiation), so the table ends before that pair.
+static int attn_append_run(const KvAttnArgs& a, hipStream_t stream) {
+  const KvAttnLimits lim = {AP_SMAX, AP_CMAX, 65535, AT_T, AP_SPAN, AT_T * AP_SLOT};
+  if (const int rc = kv_attn_check(a, lim); rc || a.B == 0) return rc;
+  static constexpr KvAttnLaunch launch[] = {   // [rows + 2 * fp8 + 4 * split]
+      attn_append_launch<false, false, false>, attn_append_launch<true, false, false>,
+      attn_append_launch<false, false, true>,  attn_append_launch<true, false, true>,
+      attn_append_launch<false, true, false>,  attn_append_launch<true, true, false>};
+  return launch[a.rows + 2 * a.fp8 + 4 * a.split](a, stream);
 }
 
 // qkv [B*C, 3*H*Dh] bf16 (q | k | v), caches [B, H, S_max, Dh] bf16, o [B*C, H*Dh] bf16, pos int32[1]:
 // every sequence appends C tokens at rows pos .. pos + C - 1
 JDT_API int jdt_attn_append(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int C,
                             int H, int Dh, int S_max, float scale, void* stream) {
-  return attn_append_launch<false>(qkv, k_cache, v_cache, o, pos, nullptr, B, C, H, Dh, S_max, scale, stream);
+  return attn_append_run({qkv, k_cache, v_cache, nullptr, nullptr, o, pos, nullptr, nullptr, 0, B, C, H, Dh, S_max,
+                          scale, false, false, false}, static_cast<hipStream_t>(stream));
 }
 
 // one position and one token count (0..C) per sequence: pos int32[B], count int32[B]
 JDT_API int jdt_attn_append_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos,
                                  const int* count, int B, int C, int H, int Dh, int S_max, float scale, void* stream) {
-  return attn_append_launch<true>(qkv, k_cache, v_cache, o, pos, count, B, C, H, Dh, S_max, scale, stream);
-}
-
-// The FP8 launchers: attn_append_launch's checks and codes, with -2 also for a null scale pointer and -6
-// for caches off an 8-byte or scales off a 4-byte boundary.
-template <bool ROWS>
-static int attn_append_fp8_launch(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
-                                  void* o, const int* pos, const int* count, int B, int C, int H, int Dh, int S_max,
-                                  float scale, void* stream) {
-  if (Dh != AT_D) return -3;
-  if (S_max < 1 || S_max > AP_SMAX) return -4;
-  if (C < 1 || C > AP_CMAX) return -11;
-  if (B < 0 || H < 1 || (long)B * H > 65535) return -5;
-  if (!qkv || !k_cache || !v_cache || !k_scale || !v_scale || !o || !pos || (ROWS && !count)) return -2;
-  if (misaligned16(qkv) || misaligned8(k_cache) || misaligned8(v_cache) || misaligned4(k_scale) ||
-      misaligned4(v_scale))
-    return -6;
-  if (B == 0) return 0;
-  hipLaunchKernelGGL((attn_append_kernel<ROWS, false, true>), dim3((C + AT_T - 1) / AT_T, B * H), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
-                     static_cast<uint8_t*>(k_cache), static_cast<uint8_t*>(v_cache), static_cast<bf16_t*>(o), pos,
-                     count, C, H, S_max, scale, k_scale, v_scale);
-  return HIP_LAUNCH_CHECK();
+  return attn_append_run({qkv, k_cache, v_cache, nullptr, nullptr, o, pos, count, nullptr, 0, B, C, H, Dh, S_max,
+                          scale, true, false, false}, static_cast<hipStream_t>(stream));
 }
 
 // jdt_attn_append on an FP8 cache: caches [B, H, S_max, Dh] e4m3 bytes, k_scale / v_scale fp32 [B, H, S_max]
 JDT_API int jdt_attn_append_fp8(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
                                 void* o, const int* pos, int B, int C, int H, int Dh, int S_max, float scale,
                                 void* stream) {
-  return attn_append_fp8_launch<false>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, nullptr, B, C, H, Dh, S_max,
-                                       scale, stream);
+  return attn_append_run({qkv, k_cache, v_cache, k_scale, v_scale, o, pos, nullptr, nullptr, 0, B, C, H, Dh, S_max,
+                          scale, false, false, true}, static_cast<hipStream_t>(stream));
 }
 
 // one position and one token count (0..C) per sequence: pos int32[B], count int32[B]
 JDT_API int jdt_attn_append_fp8_rows(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
                                      void* o, const int* pos, const int* count, int B, int C, int H, int Dh,
                                      int S_max, float scale, void* stream) {
-  return attn_append_fp8_launch<true>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, count, B, C, H, Dh, S_max,
-                                      scale, stream);
-}
-
-// Split-KV: the split launch, then the combine on the same stream.  The checks and codes of
-// attn_append_launch, plus -2 for a null ws and -10 for a workspace below B * H * ceil(C / 64) *
-// ceil(S_max / 512) * 64 * 66 floats; everything is checked before anything is launched.
-template <bool ROWS>
-static int attn_append_split_launch(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos,
-                                    const int* count, float* ws, long ws_floats, int B, int C, int H, int Dh, int S_max,
-                                    float scale, void* stream) {
-  if (Dh != AT_D) return -3;
-  if (S_max < 1 || S_max > AP_SMAX) return -4;
-  if (C < 1 || C > AP_CMAX) return -11;
-  if (B < 0 || H < 1 || (long)B * H > 65535) return -5;
-  if (!qkv || !k_cache || !v_cache || !o || !pos || (ROWS && !count) || !ws) return -2;
-  if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
-  const int n_qt = (C + AT_T - 1) / AT_T, n_spans = (S_max + AP_SPAN - 1) / AP_SPAN;
-  if (ws_floats < (long)B * H * n_qt * n_spans * AT_T * AP_SLOT) return -10;
-  if (B == 0) return 0;
-  hipLaunchKernelGGL((attn_append_kernel<ROWS, true, false>), dim3(n_qt, B * H, n_spans), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv), static_cast<bf16_t*>(k_cache),
-                     static_cast<bf16_t*>(v_cache), ws, pos, count, C, H, S_max, scale, static_cast<float*>(nullptr),
-                     static_cast<float*>(nullptr));
-  const int rc = HIP_LAUNCH_CHECK();
-  if (rc) return rc;
-  hipLaunchKernelGGL(attn_append_combine_kernel<ROWS>, dim3(n_qt, B * H), dim3(1024), 0,
-                     static_cast<hipStream_t>(stream), static_cast<const float*>(ws), static_cast<bf16_t*>(o), pos,
-                     count, C, H, S_max, n_spans);
-  return HIP_LAUNCH_CHECK();
+  return attn_append_run({qkv, k_cache, v_cache, k_scale, v_scale, o, pos, count, nullptr, 0, B, C, H, Dh, S_max,
+                          scale, true, false, true}, static_cast<hipStream_t>(stream));
 }
 
 // jdt_attn_append through the split-KV pair: ws is fp32 scratch of ws_floats >= B * H * ceil(C / 64) *
 // ceil(S_max / 512) * 64 * 66 words (any contents; one slot per row of a workgroup of the split launch)
 JDT_API int jdt_attn_append_split(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, float* ws,
                                   long ws_floats, int B, int C, int H, int Dh, int S_max, float scale, void* stream) {
-  return attn_append_split_launch<false>(qkv, k_cache, v_cache, o, pos, nullptr, ws, ws_floats, B, C, H, Dh, S_max,
-                                         scale, stream);
+  return attn_append_run({qkv, k_cache, v_cache, nullptr, nullptr, o, pos, nullptr, ws, ws_floats, B, C, H, Dh, S_max,
+                          scale, false, true, false}, static_cast<hipStream_t>(stream));
 }
 
 // as jdt_attn_append_split with one position and one token count per sequence: pos int32[B], count int32[B]
 JDT_API int jdt_attn_append_split_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos,
                                        const int* count, float* ws, long ws_floats, int B, int C, int H, int Dh,
                                        int S_max, float scale, void* stream) {
-  return attn_append_split_launch<true>(qkv, k_cache, v_cache, o, pos, count, ws, ws_floats, B, C, H, Dh, S_max,
-                                        scale, stream);
+  return attn_append_run({qkv, k_cache, v_cache, nullptr, nullptr, o, pos, count, ws, ws_floats, B, C, H, Dh, S_max,
+                          scale, true, true, false}, static_cast<hipStream_t>(stream));
 }

@@ -388,150 +388,101 @@ __global__ void __launch_bounds__(256) sample_kernel(const bf16_t* __restrict__ 
 }  // namespace jdt
 using namespace jdt;
 
-template <bool ROWS>
-static int attn_decode_launch(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H,
-                              int Dh, int S_max, float scale, void* stream) {
-  if (Dh != AD_DH) return -3;
-  if (S_max < 1 || S_max > AD_SMAX) return -4;
-  if (B < 0 || H < 1) return -5;
-  if (!qkv || !k_cache || !v_cache || !o || !pos) return -2;
-  if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
-  if (B == 0) return 0;
-  hipLaunchKernelGGL((attn_decode_kernel<ROWS, false, false>), dim3(B * H), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
-                     static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache), static_cast<bf16_t*>(o), pos, H,
-                     S_max, scale, static_cast<float*>(nullptr), static_cast<float*>(nullptr),
-                     static_cast<float*>(nullptr));
-  return HIP_LAUNCH_CHECK();
+#include "kv_launch.h"
+
+// One instantiation's launch: attn_decode_kernel<ROWS, SPLIT, FP8>, one workgroup per (batch, head) and,
+// SPLIT, per 128-key chunk, then the combine on the same stream.
+template <bool ROWS, bool SPLIT, bool FP8>
+static int attn_decode_launch(const KvAttnArgs& a, hipStream_t stream) {
+  using cache_t = std::conditional_t<FP8, uint8_t, bf16_t>;
+  const int n_chunks = SPLIT ? (a.S_max + AD_CHUNK - 1) / AD_CHUNK : 1;
+  hipLaunchKernelGGL((attn_decode_kernel<ROWS, SPLIT, FP8>), dim3(a.B * a.H, n_chunks), dim3(256), 0, stream,
+                     static_cast<const bf16_t*>(a.qkv), static_cast<cache_t*>(a.k_cache),
+                     static_cast<cache_t*>(a.v_cache), static_cast<bf16_t*>(SPLIT ? nullptr : a.o), a.pos, a.H,
+                     a.S_max, a.scale, a.ws, a.k_scale, a.v_scale);
+  int rc = HIP_LAUNCH_CHECK();
+  if constexpr (SPLIT) {
+    if (rc) return rc;
+    hipLaunchKernelGGL(attn_decode_combine_kernel<ROWS>, dim3(a.B * a.H), dim3(WAVE), 0, stream,
+                       static_cast<const float*>(a.ws), static_cast<bf16_t*>(a.o), a.pos, a.H, a.S_max, n_chunks);
+    rc = HIP_LAUNCH_CHECK();
+  }
+  return rc;
+}
+
+// The eight decode entry points: kv_attn_check's ladder (one launch: caches of up to 128 rows; split: 32768
+// and a workspace of B * H * ceil(S_max / 128) * 66 floats), then the instantiation the flags name.
+static int attn_decode_run(const KvAttnArgs& a, hipStream_t stream) {
+  const KvAttnLimits lim = {a.split ? AD_LONG_SMAX : AD_SMAX, 0, INT_MAX, 1, AD_CHUNK, AD_SLOT};
+  if (const int rc = kv_attn_check(a, lim); rc || a.B == 0) return rc;
+  static constexpr KvAttnLaunch launch[] = {   // [rows + 2 * split + 4 * fp8]
+      attn_decode_launch<false, false, false>, attn_decode_launch<true, false, false>,
+      attn_decode_launch<false, true, false>,  attn_decode_launch<true, true, false>,
+      attn_decode_launch<false, false, true>,  attn_decode_launch<true, false, true>,
+      attn_decode_launch<false, true, true>,   attn_decode_launch<true, true, true>};
+  return launch[a.rows + 2 * a.split + 4 * a.fp8](a, stream);
 }
 
 // qkv [B, 3*H*Dh] bf16 (q | k | v), caches [B, H, S_max, Dh] bf16, o [B, H*Dh] bf16, pos int32[1]
 JDT_API int jdt_attn_decode(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H,
                             int Dh, int S_max, float scale, void* stream) {
-  return attn_decode_launch<false>(qkv, k_cache, v_cache, o, pos, B, H, Dh, S_max, scale, stream);
+  return attn_decode_run({qkv, k_cache, v_cache, nullptr, nullptr, o, pos, nullptr, nullptr, 0, B, 0, H, Dh, S_max,
+                          scale, false, false, false}, static_cast<hipStream_t>(stream));
 }
 
 // as jdt_attn_decode with one position per sequence: pos int32[B]
 JDT_API int jdt_attn_decode_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, int B, int H,
                                  int Dh, int S_max, float scale, void* stream) {
-  return attn_decode_launch<true>(qkv, k_cache, v_cache, o, pos, B, H, Dh, S_max, scale, stream);
-}
-
-// Split-KV: the split launch, then the combine on the same stream.  Everything is checked
-// before anything is launched; -10: a workspace below B * H * ceil(S_max / 128) * 66 floats.
-template <bool ROWS>
-static int attn_decode_long_launch(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, float* ws,
-                                   long ws_floats, int B, int H, int Dh, int S_max, float scale, void* stream) {
-  if (Dh != AD_DH) return -3;
-  if (S_max < 1 || S_max > AD_LONG_SMAX) return -4;
-  if (B < 0 || H < 1 || (long)B * H > INT_MAX) return -5;
-  if (!qkv || !k_cache || !v_cache || !o || !pos || !ws) return -2;
-  if (misaligned16(qkv) || misaligned16(k_cache) || misaligned16(v_cache)) return -6;
-  const int n_chunks = (S_max + AD_CHUNK - 1) / AD_CHUNK;
-  if (ws_floats < (long)B * H * n_chunks * AD_SLOT) return -10;
-  if (B == 0) return 0;
-  hipLaunchKernelGGL((attn_decode_kernel<ROWS, true, false>), dim3(B * H, n_chunks), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
-                     static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache), static_cast<bf16_t*>(nullptr), pos,
-                     H, S_max, scale, ws, static_cast<float*>(nullptr), static_cast<float*>(nullptr));
-  const int rc = HIP_LAUNCH_CHECK();
-  if (rc) return rc;
-  hipLaunchKernelGGL(attn_decode_combine_kernel<ROWS>, dim3(B * H), dim3(WAVE), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const float*>(ws), static_cast<bf16_t*>(o), pos, H, S_max, n_chunks);
-  return HIP_LAUNCH_CHECK();
+  return attn_decode_run({qkv, k_cache, v_cache, nullptr, nullptr, o, pos, nullptr, nullptr, 0, B, 0, H, Dh, S_max,
+                          scale, true, false, false}, static_cast<hipStream_t>(stream));
 }
 
 // jdt_attn_decode for caches of 1 <= S_max <= 32768 rows: ws is fp32 scratch of ws_floats >=
 // B * H * ceil(S_max / 128) * 66 words (any contents; one slot per workgroup of the split launch)
 JDT_API int jdt_attn_decode_long(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos, float* ws,
                                  long ws_floats, int B, int H, int Dh, int S_max, float scale, void* stream) {
-  return attn_decode_long_launch<false>(qkv, k_cache, v_cache, o, pos, ws, ws_floats, B, H, Dh, S_max, scale, stream);
+  return attn_decode_run({qkv, k_cache, v_cache, nullptr, nullptr, o, pos, nullptr, ws, ws_floats, B, 0, H, Dh, S_max,
+                          scale, false, true, false}, static_cast<hipStream_t>(stream));
 }
 
 // as jdt_attn_decode_long with one position per sequence: pos int32[B]
 JDT_API int jdt_attn_decode_long_rows(const void* qkv, void* k_cache, void* v_cache, void* o, const int* pos,
                                       float* ws, long ws_floats, int B, int H, int Dh, int S_max, float scale,
                                       void* stream) {
-  return attn_decode_long_launch<true>(qkv, k_cache, v_cache, o, pos, ws, ws_floats, B, H, Dh, S_max, scale, stream);
-}
-
-// The FP8 launchers: the bf16 ones' checks and codes, with -2 also for a null scale pointer and -6 for
-// caches off an 8-byte or scales off a 4-byte boundary.
-template <bool ROWS>
-static int attn_decode_fp8_launch(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
-                                  void* o, const int* pos, int B, int H, int Dh, int S_max, float scale,
-                                  void* stream) {
-  if (Dh != AD_DH) return -3;
-  if (S_max < 1 || S_max > AD_SMAX) return -4;
-  if (B < 0 || H < 1) return -5;
-  if (!qkv || !k_cache || !v_cache || !k_scale || !v_scale || !o || !pos) return -2;
-  if (misaligned16(qkv) || misaligned8(k_cache) || misaligned8(v_cache) || misaligned4(k_scale) ||
-      misaligned4(v_scale))
-    return -6;
-  if (B == 0) return 0;
-  hipLaunchKernelGGL((attn_decode_kernel<ROWS, false, true>), dim3(B * H), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
-                     static_cast<uint8_t*>(k_cache), static_cast<uint8_t*>(v_cache), static_cast<bf16_t*>(o), pos, H,
-                     S_max, scale, static_cast<float*>(nullptr), k_scale, v_scale);
-  return HIP_LAUNCH_CHECK();
+  return attn_decode_run({qkv, k_cache, v_cache, nullptr, nullptr, o, pos, nullptr, ws, ws_floats, B, 0, H, Dh, S_max,
+                          scale, true, true, false}, static_cast<hipStream_t>(stream));
 }
 
 // jdt_attn_decode on an FP8 cache: caches [B, H, S_max, Dh] e4m3 bytes, k_scale / v_scale fp32 [B, H, S_max]
 JDT_API int jdt_attn_decode_fp8(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
                                 void* o, const int* pos, int B, int H, int Dh, int S_max, float scale,
                                 void* stream) {
-  return attn_decode_fp8_launch<false>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, B, H, Dh, S_max, scale,
-                                       stream);
+  return attn_decode_run({qkv, k_cache, v_cache, k_scale, v_scale, o, pos, nullptr, nullptr, 0, B, 0, H, Dh, S_max,
+                          scale, false, false, true}, static_cast<hipStream_t>(stream));
 }
 
 // as jdt_attn_decode_fp8 with one position per sequence: pos int32[B]
 JDT_API int jdt_attn_decode_fp8_rows(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
                                      void* o, const int* pos, int B, int H, int Dh, int S_max, float scale,
                                      void* stream) {
-  return attn_decode_fp8_launch<true>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, B, H, Dh, S_max, scale,
-                                      stream);
-}
-
-// Split-KV on an FP8 cache: the same 128-key chunks, workspace and combine as the bf16 pair.
-template <bool ROWS>
-static int attn_decode_fp8_long_launch(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
-                                       void* o, const int* pos, float* ws, long ws_floats, int B, int H, int Dh,
-                                       int S_max, float scale, void* stream) {
-  if (Dh != AD_DH) return -3;
-  if (S_max < 1 || S_max > AD_LONG_SMAX) return -4;
-  if (B < 0 || H < 1 || (long)B * H > INT_MAX) return -5;
-  if (!qkv || !k_cache || !v_cache || !k_scale || !v_scale || !o || !pos || !ws) return -2;
-  if (misaligned16(qkv) || misaligned8(k_cache) || misaligned8(v_cache) || misaligned4(k_scale) ||
-      misaligned4(v_scale))
-    return -6;
-  const int n_chunks = (S_max + AD_CHUNK - 1) / AD_CHUNK;
-  if (ws_floats < (long)B * H * n_chunks * AD_SLOT) return -10;
-  if (B == 0) return 0;
-  hipLaunchKernelGGL((attn_decode_kernel<ROWS, true, true>), dim3(B * H, n_chunks), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), static_cast<const bf16_t*>(qkv),
-                     static_cast<uint8_t*>(k_cache), static_cast<uint8_t*>(v_cache), static_cast<bf16_t*>(nullptr),
-                     pos, H, S_max, scale, ws, k_scale, v_scale);
-  const int rc = HIP_LAUNCH_CHECK();
-  if (rc) return rc;
-  hipLaunchKernelGGL(attn_decode_combine_kernel<ROWS>, dim3(B * H), dim3(WAVE), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const float*>(ws), static_cast<bf16_t*>(o), pos, H, S_max, n_chunks);
-  return HIP_LAUNCH_CHECK();
+  return attn_decode_run({qkv, k_cache, v_cache, k_scale, v_scale, o, pos, nullptr, nullptr, 0, B, 0, H, Dh, S_max,
+                          scale, true, false, true}, static_cast<hipStream_t>(stream));
 }
 
 // jdt_attn_decode_long on an FP8 cache
 JDT_API int jdt_attn_decode_fp8_long(const void* qkv, void* k_cache, void* v_cache, float* k_scale, float* v_scale,
                                      void* o, const int* pos, float* ws, long ws_floats, int B, int H, int Dh,
                                      int S_max, float scale, void* stream) {
-  return attn_decode_fp8_long_launch<false>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, ws, ws_floats, B, H, Dh,
-                                            S_max, scale, stream);
+  return attn_decode_run({qkv, k_cache, v_cache, k_scale, v_scale, o, pos, nullptr, ws, ws_floats, B, 0, H, Dh, S_max,
+                          scale, false, true, true}, static_cast<hipStream_t>(stream));
 }
 
 // as jdt_attn_decode_fp8_long with one position per sequence: pos int32[B]
 JDT_API int jdt_attn_decode_fp8_long_rows(const void* qkv, void* k_cache, void* v_cache, float* k_scale,
                                           float* v_scale, void* o, const int* pos, float* ws, long ws_floats, int B,
                                           int H, int Dh, int S_max, float scale, void* stream) {
-  return attn_decode_fp8_long_launch<true>(qkv, k_cache, v_cache, k_scale, v_scale, o, pos, ws, ws_floats, B, H, Dh,
-                                           S_max, scale, stream);
+  return attn_decode_run({qkv, k_cache, v_cache, k_scale, v_scale, o, pos, nullptr, ws, ws_floats, B, 0, H, Dh, S_max,
+                          scale, true, true, true}, static_cast<hipStream_t>(stream));
 }
 
 template <bool ROWS>

@@ -1084,6 +1084,27 @@ def _is_fp8_cache(k_cache, v_cache, k_scale, v_scale) -> bool:
     return fp8
 
 
+def _kv_attn_launch(append: bool, rows: bool, qkv, k_cache, v_cache, k_scale, v_scale, out, pos, count, ws, dims):
+    """The one launch site of ``attention_decode`` / ``attention_append``: the entry point of
+    csrc/attn_decode.hip or csrc/attn_append.hip that (append, fp8, split, rows) names (``_lib._kv_attn_name``;
+    fp8: the scales are given, split: ``ws`` is), with its arguments in that variant's order.  ``dims``:
+    (B, [C,] H, Dh, S_max)."""
+    fp8, split = k_scale is not None, ws is not None
+    for t in (qkv, k_cache, v_cache, out) + ((k_scale, v_scale) if fp8 else ()):
+        assert t.is_contiguous()
+    assert qkv.dtype == out.dtype == torch.bfloat16
+    assert k_cache.dtype == v_cache.dtype == (torch.uint8 if fp8 else torch.bfloat16)
+    if split:
+        assert ws.is_contiguous() and ws.dtype == torch.float32 and ws.device == qkv.device
+    name = _lib._kv_attn_name(append, fp8, split, rows)
+    args = (_ptr(qkv), _ptr(k_cache), _ptr(v_cache)) + ((_ptr(k_scale), _ptr(v_scale)) if fp8 else ())
+    args += (_ptr(out), _ptr(pos)) + ((_ptr(count),) if append and rows else ())
+    Dh = dims[-2]
+    args += ((_ptr(ws), ws.numel()) if split else ()) + dims + (float(1.0 / (Dh ** 0.5)), _lib.stream_ptr())
+    rc = getattr(_lib.lib(), name)(*args)
+    _lib.check(rc, name)
+
+
 def kv_cache_fill(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor,
                   v_scale: torch.Tensor, n: int, Sp: int):
     """Prefill copy into one layer's FP8 cache: rows < ``n`` of every (sequence, head) of ``k_cache`` /
@@ -1165,48 +1186,18 @@ def attention_decode(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     d = d3 // 3
     Dh = d // H
     assert k_cache.shape == v_cache.shape and k_cache.shape[:2] == (B, H) and k_cache.shape[3] == Dh
-    fp8 = _is_fp8_cache(k_cache, v_cache, k_scale, v_scale)
+    _is_fp8_cache(k_cache, v_cache, k_scale, v_scale)
     rows = _per_row(pos, B)
     S_max = k_cache.shape[2]
     if out is None:
         out = torch.zeros(B, d, dtype=torch.bfloat16, device=qkv.device)
     if not _is_gpu(qkv) or Dh != AD_HEAD_DIM or S_max > AD_LONG_MAX_ROWS:
         return _attention_decode_torch(qkv, k_cache, v_cache, pos, H, out, k_scale, v_scale)
-    if fp8:
-        for t in (qkv, k_cache, v_cache, k_scale, v_scale, out):
-            assert t.is_contiguous()
-        assert qkv.dtype == out.dtype == torch.bfloat16
-        scale = float(1.0 / (Dh ** 0.5))
-        if S_max <= AD_MAX_ROWS:
-            name = "jdt_attn_decode_fp8_rows" if rows else "jdt_attn_decode_fp8"
-            rc = getattr(_lib.lib(), name)(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
-                                           _ptr(out), _ptr(pos), B, H, Dh, S_max, scale, _lib.stream_ptr())
-            _lib.check(rc, name)
-            return out
-        if ws is None:
-            ws = _decode_workspace(qkv.device, attention_decode_ws_floats(B, H, S_max))
-        assert ws.is_contiguous() and ws.dtype == torch.float32 and ws.device == qkv.device
-        name = "jdt_attn_decode_fp8_long_rows" if rows else "jdt_attn_decode_fp8_long"
-        rc = getattr(_lib.lib(), name)(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
-                                       _ptr(out), _ptr(pos), _ptr(ws), ws.numel(), B, H, Dh, S_max, scale,
-                                       _lib.stream_ptr())
-        _lib.check(rc, name)
-        return out
-    for t in (qkv, k_cache, v_cache, out):
-        assert t.is_contiguous() and t.dtype == torch.bfloat16
     if S_max <= AD_MAX_ROWS:
-        name = "jdt_attn_decode_rows" if rows else "jdt_attn_decode"
-        rc = getattr(_lib.lib(), name)(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos), B, H, Dh,
-                                       S_max, float(1.0 / (Dh ** 0.5)), _lib.stream_ptr())
-        _lib.check(rc, name)
-        return out
-    if ws is None:
+        ws = None   # one launch: the workspace is ignored
+    elif ws is None:
         ws = _decode_workspace(qkv.device, attention_decode_ws_floats(B, H, S_max))
-    assert ws.is_contiguous() and ws.dtype == torch.float32 and ws.device == qkv.device
-    name = "jdt_attn_decode_long_rows" if rows else "jdt_attn_decode_long"
-    rc = getattr(_lib.lib(), name)(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos), _ptr(ws),
-                                   ws.numel(), B, H, Dh, S_max, float(1.0 / (Dh ** 0.5)), _lib.stream_ptr())
-    _lib.check(rc, name)
+    _kv_attn_launch(False, rows, qkv, k_cache, v_cache, k_scale, v_scale, out, pos, None, ws, (B, H, Dh, S_max))
     return out
 
 
@@ -1355,45 +1346,9 @@ def attention_append(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
         raise ValueError("split append (ws) does not take FP8 caches")
     if not _is_gpu(qkv) or Dh != AD_HEAD_DIM or S_max > AP_MAX_ROWS or C > AP_MAX_CHUNK:
         return _attention_append_torch(qkv, k_cache, v_cache, pos, H, C, count, rows, out, k_scale, v_scale)
-    if fp8:
-        for t in (qkv, k_cache, v_cache, k_scale, v_scale, out):
-            assert t.is_contiguous()
-        assert qkv.dtype == out.dtype == torch.bfloat16
-        scale = float(1.0 / (Dh ** 0.5))
-        if rows:
-            rc = _lib.lib().jdt_attn_append_fp8_rows(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale),
-                                                     _ptr(v_scale), _ptr(out), _ptr(pos), _ptr(count), B, C, H, Dh,
-                                                     S_max, scale, _lib.stream_ptr())
-            _lib.check(rc, "jdt_attn_append_fp8_rows")
-        else:
-            rc = _lib.lib().jdt_attn_append_fp8(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale),
-                                                _ptr(out), _ptr(pos), B, C, H, Dh, S_max, scale, _lib.stream_ptr())
-            _lib.check(rc, "jdt_attn_append_fp8")
-        return out
-    for t in (qkv, k_cache, v_cache, out):
-        assert t.is_contiguous() and t.dtype == torch.bfloat16
-    scale = float(1.0 / (Dh ** 0.5))
     if ws is not None:
-        assert ws.is_contiguous() and ws.dtype == torch.float32 and ws.device == qkv.device
         assert ws.numel() >= attention_append_ws_floats(B, H, C, S_max), "ws is below attention_append_ws_floats"
-        if rows:
-            rc = _lib.lib().jdt_attn_append_split_rows(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos),
-                                                       _ptr(count), _ptr(ws), ws.numel(), B, C, H, Dh, S_max, scale,
-                                                       _lib.stream_ptr())
-            _lib.check(rc, "jdt_attn_append_split_rows")
-        else:
-            rc = _lib.lib().jdt_attn_append_split(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos),
-                                                  _ptr(ws), ws.numel(), B, C, H, Dh, S_max, scale, _lib.stream_ptr())
-            _lib.check(rc, "jdt_attn_append_split")
-        return out
-    if rows:
-        rc = _lib.lib().jdt_attn_append_rows(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos),
-                                             _ptr(count), B, C, H, Dh, S_max, scale, _lib.stream_ptr())
-        _lib.check(rc, "jdt_attn_append_rows")
-    else:
-        rc = _lib.lib().jdt_attn_append(_ptr(qkv), _ptr(k_cache), _ptr(v_cache), _ptr(out), _ptr(pos), B, C, H, Dh,
-                                        S_max, scale, _lib.stream_ptr())
-        _lib.check(rc, "jdt_attn_append")
+    _kv_attn_launch(True, rows, qkv, k_cache, v_cache, k_scale, v_scale, out, pos, count, ws, (B, C, H, Dh, S_max))
     return out
 
 

@@ -93,6 +93,133 @@ static int failures = 0;
     }                                                        \
   } while (0)
 
+alignas(16) static unsigned char buf[64];
+
+// The 14 KV-cache attention launchers (attn_decode.hip, attn_append.hip) share one ladder of checks, so one
+// list of cases runs over every variant: KvArgs holds every argument any of them takes, a variant's ``call``
+// passes on the ones its entry point has.
+struct KvArgs {
+  const void* qkv;
+  void *k_cache, *v_cache;
+  float *k_scale, *v_scale;
+  void* o;
+  const int *pos, *count;
+  float* ws;
+  long ws_floats;
+  int B, C, H, Dh, S_max;
+};
+struct KvVariant {
+  const char* name;
+  int (*call)(const KvArgs&);
+  bool rows, split, fp8;
+};
+#define KV_DECODE(fn, ...) [](const KvArgs& a) { return fn(__VA_ARGS__, a.B, a.H, a.Dh, a.S_max, .125f, nullptr); }
+#define KV_APPEND(fn, ...) [](const KvArgs& a) { return fn(__VA_ARGS__, a.B, a.C, a.H, a.Dh, a.S_max, .125f, nullptr); }
+static const KvVariant kv_decode[] = {
+    {"attn_decode", KV_DECODE(jdt_attn_decode, a.qkv, a.k_cache, a.v_cache, a.o, a.pos), false, false, false},
+    {"attn_decode_rows", KV_DECODE(jdt_attn_decode_rows, a.qkv, a.k_cache, a.v_cache, a.o, a.pos), true, false, false},
+    {"attn_decode_long", KV_DECODE(jdt_attn_decode_long, a.qkv, a.k_cache, a.v_cache, a.o, a.pos, a.ws, a.ws_floats),
+     false, true, false},
+    {"attn_decode_long_rows",
+     KV_DECODE(jdt_attn_decode_long_rows, a.qkv, a.k_cache, a.v_cache, a.o, a.pos, a.ws, a.ws_floats), true, true,
+     false},
+    {"attn_decode_fp8", KV_DECODE(jdt_attn_decode_fp8, a.qkv, a.k_cache, a.v_cache, a.k_scale, a.v_scale, a.o, a.pos),
+     false, false, true},
+    {"attn_decode_fp8_rows",
+     KV_DECODE(jdt_attn_decode_fp8_rows, a.qkv, a.k_cache, a.v_cache, a.k_scale, a.v_scale, a.o, a.pos), true, false,
+     true},
+    {"attn_decode_fp8_long", KV_DECODE(jdt_attn_decode_fp8_long, a.qkv, a.k_cache, a.v_cache, a.k_scale, a.v_scale, a.o,
+                                       a.pos, a.ws, a.ws_floats),
+     false, true, true},
+    {"attn_decode_fp8_long_rows", KV_DECODE(jdt_attn_decode_fp8_long_rows, a.qkv, a.k_cache, a.v_cache, a.k_scale,
+                                            a.v_scale, a.o, a.pos, a.ws, a.ws_floats),
+     true, true, true},
+};
+static const KvVariant kv_append[] = {
+    {"attn_append", KV_APPEND(jdt_attn_append, a.qkv, a.k_cache, a.v_cache, a.o, a.pos), false, false, false},
+    {"attn_append_rows", KV_APPEND(jdt_attn_append_rows, a.qkv, a.k_cache, a.v_cache, a.o, a.pos, a.count), true, false,
+     false},
+    {"attn_append_split", KV_APPEND(jdt_attn_append_split, a.qkv, a.k_cache, a.v_cache, a.o, a.pos, a.ws, a.ws_floats),
+     false, true, false},
+    {"attn_append_split_rows",
+     KV_APPEND(jdt_attn_append_split_rows, a.qkv, a.k_cache, a.v_cache, a.o, a.pos, a.count, a.ws, a.ws_floats), true,
+     true, false},
+    {"attn_append_fp8", KV_APPEND(jdt_attn_append_fp8, a.qkv, a.k_cache, a.v_cache, a.k_scale, a.v_scale, a.o, a.pos),
+     false, false, true},
+    {"attn_append_fp8_rows",
+     KV_APPEND(jdt_attn_append_fp8_rows, a.qkv, a.k_cache, a.v_cache, a.k_scale, a.v_scale, a.o, a.pos, a.count), true,
+     false, true},
+};
+
+static void kv_expect(const KvVariant& v, const KvArgs& a, int want, const char* what) {
+  const int got = v.call(a);
+  if (got != want) {
+    std::fprintf(stderr, "FAIL: %s %s: returned %d, expected %d\n", v.name, what, got, want);
+    ++failures;
+  }
+}
+
+// Every variant of a family against the whole ladder, in the ladder's order: head dim 64 (-3), S_max in 1..top
+// with top = 128 for the one-launch decode and 32768 otherwise (-4), append: C in 1..1024 (-11), B >= 0, H >= 1
+// and B * H within the grid: INT_MAX for decode, 65535 for append (-5), the pointers the variant takes (-2),
+// alignment (-6), split: the workspace (-10), and B = 0 as a no-op.  Each case changes ``ok``, arguments the
+// variant accepts (and would launch with: never passed as they are), in the one way it names.
+static void kv_check_family(const KvVariant* variants, int n, bool append) {
+  int* ip = reinterpret_cast<int*>(buf);
+  float* fp = reinterpret_cast<float*>(buf);
+  const long big = 1L << 40;   // a workspace size no shape here exceeds
+  for (int i = 0; i < n; ++i) {
+    const KvVariant& v = variants[i];
+    const int s_top = append || v.split ? 32768 : 128;
+    // B = 1, H = 2; decode: 3 chunks of 128 keys x 66 floats; append: 1 query tile x 1 span of 512 keys x 64 x 66
+    const long need = append ? 2 * 64 * 66 : 2 * 3 * 66;
+    const KvArgs ok = {buf, buf, buf, fp, fp, buf, ip, ip, fp, need, 1, 64, 2, 64, s_top == 128 ? 128 : 320};
+#define KV_CASE(edit, want, what) \
+  do {                            \
+    KvArgs c = ok;                \
+    edit;                         \
+    kv_expect(v, c, want, what);  \
+  } while (0)
+    KV_CASE(c.Dh = 32, -3, "rejects head dim 32");
+    KV_CASE(c.Dh = 128, -3, "rejects head dim 128");
+    KV_CASE((c.Dh = 32, c.S_max = 0, c.B = -1, c.qkv = nullptr), -3, "checks the head dim first");
+    KV_CASE(c.S_max = 0, -4, "rejects S_max 0");
+    KV_CASE((c.S_max = s_top + 1, c.ws_floats = big), -4, "rejects S_max past its envelope");
+    if (append) {
+      KV_CASE(c.C = 0, -11, "rejects C 0");
+      KV_CASE((c.C = 1025, c.ws_floats = big), -11, "rejects C 1025");
+    }
+    KV_CASE((c.B = 65536, c.H = append ? 1 : 65536, c.ws_floats = big), -5, "rejects B * H past the grid");
+    KV_CASE(c.B = -1, -5, "rejects B < 0");
+    KV_CASE(c.H = 0, -5, "rejects H 0");
+    KV_CASE(c.qkv = nullptr, -2, "rejects a null qkv");
+    KV_CASE(c.k_cache = nullptr, -2, "rejects a null k_cache");
+    KV_CASE(c.v_cache = nullptr, -2, "rejects a null v_cache");
+    KV_CASE(c.o = nullptr, -2, "rejects a null o");
+    KV_CASE(c.pos = nullptr, -2, "rejects a null pos");
+    KV_CASE(c.qkv = buf + 4, -6, "rejects a misaligned qkv");
+    KV_CASE(c.k_cache = buf + 4, -6, "rejects a misaligned k_cache");
+    KV_CASE(c.v_cache = buf + 4, -6, "rejects a misaligned v_cache");
+    KV_CASE((c.k_cache = c.v_cache = buf + 8, c.B = 0), v.fp8 ? 0 : -6, "takes 8-byte aligned caches as FP8 only");
+    KV_CASE((c.B = 0, c.ws_floats = 0), 0, "B = 0 is a no-op");
+    if (append && v.rows) KV_CASE(c.count = nullptr, -2, "rejects a null count");
+    if (v.fp8) {
+      KV_CASE(c.k_scale = nullptr, -2, "rejects a null k_scale");
+      KV_CASE(c.v_scale = nullptr, -2, "rejects a null v_scale");
+      KV_CASE(c.k_scale = reinterpret_cast<float*>(buf + 2), -6, "rejects a misaligned k_scale");
+      KV_CASE(c.v_scale = reinterpret_cast<float*>(buf + 2), -6, "rejects a misaligned v_scale");
+    }
+    if (v.split) {
+      KV_CASE(c.ws = nullptr, -2, "rejects a null ws");
+      KV_CASE(c.ws_floats = need - 1, -10, "rejects a short ws");
+      KV_CASE((c.S_max = append ? 513 : 385, c.ws_floats = append ? 2 * need - 1 : need + 2 * 66 - 1), -10,
+              "rejects a ws short of one more span");
+      if (append) KV_CASE((c.C = 65, c.ws_floats = 2 * need - 1), -10, "rejects a ws short of the second query tile");
+    }
+#undef KV_CASE
+  }
+}
+
 int main() {
   // layout probes (the Python ctypes mirrors compare against these)
   EXPECT(jdt_gemm_args_size() > 0 && jdt_mlp2_args_size() > 0 && jdt_md_args_size() > 0, "struct sizes");
@@ -123,17 +250,12 @@ int main() {
   EXPECT(jdt_sgd(nullptr, nullptr, nullptr, nullptr, 0, .1f, 0.f, 0.f, 1.f, nullptr, nullptr, 1, nullptr) == 0,
          "sgd n = 0 is a no-op");
   EXPECT(jdt_colsum(handles, 7, 4, 7, nullptr, nullptr) == -3, "colsum rejects N % 8");
-  // decode launchers (attn_decode.hip): the envelope is checked before anything is launched
-  alignas(16) unsigned char buf[64];
+  // the KV-cache attention launchers: the envelope is checked before anything is launched
+  kv_check_family(kv_decode, 8, false);
+  kv_check_family(kv_append, 6, true);
+  // the other decode launchers (attn_decode.hip): embedding and samplers
   int* ip = reinterpret_cast<int*>(buf);
   unsigned* up = reinterpret_cast<unsigned*>(buf);
-  EXPECT(jdt_attn_decode(buf, buf, buf, buf, ip, 1, 2, 32, 128, .125f, nullptr) == -3, "attn_decode rejects head dim 32");
-  EXPECT(jdt_attn_decode(buf, buf, buf, buf, ip, 1, 2, 64, 129, .125f, nullptr) == -4, "attn_decode rejects S_max > 128");
-  EXPECT(jdt_attn_decode(buf, buf, buf, buf, ip, 1, 2, 64, 0, .125f, nullptr) == -4, "attn_decode rejects S_max 0");
-  EXPECT(jdt_attn_decode(buf, nullptr, buf, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -2, "attn_decode rejects null");
-  EXPECT(jdt_attn_decode(buf + 4, buf, buf, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -6,
-         "attn_decode rejects a misaligned qkv");
-  EXPECT(jdt_attn_decode(buf, buf, buf, buf, ip, 0, 2, 64, 128, .125f, nullptr) == 0, "attn_decode B = 0 is a no-op");
   EXPECT(jdt_embed_decode(ip, buf, buf, buf, ip, 1, 128, 60, 8, nullptr) == -3, "embed_decode rejects d % 8");
   EXPECT(jdt_embed_decode(ip, buf, buf, buf, ip, 0, 128, 64, 8, nullptr) == 0, "embed_decode B = 0 is a no-op");
   EXPECT(jdt_sample(buf, 8, 1, 0, 0.f, 0, 0, ip, 128, ip, up, nullptr) == -5, "sample rejects V = 0");
@@ -141,16 +263,6 @@ int main() {
   EXPECT(jdt_sample(buf, 8, 1, 8, 1.f, 0, 0, ip, 128, ip, nullptr, nullptr) == -2, "sample rejects a null ticket");
   EXPECT(jdt_sample(buf, 8, 0, 8, 1.f, 0, 0, ip, 128, ip, up, nullptr) == 0, "sample B = 0 is a no-op");
   // per-row and filtered variants: the same envelope, plus top_k / top_p
-  EXPECT(jdt_attn_decode_rows(buf, buf, buf, buf, ip, 1, 2, 32, 128, .125f, nullptr) == -3,
-         "attn_decode_rows rejects head dim 32");
-  EXPECT(jdt_attn_decode_rows(buf, buf, buf, buf, ip, 1, 2, 64, 129, .125f, nullptr) == -4,
-         "attn_decode_rows rejects S_max > 128");
-  EXPECT(jdt_attn_decode_rows(buf, buf, buf, buf, ip, 1, 2, 64, 0, .125f, nullptr) == -4,
-         "attn_decode_rows rejects S_max 0");
-  EXPECT(jdt_attn_decode_rows(buf, buf, buf, buf, nullptr, 1, 2, 64, 128, .125f, nullptr) == -2,
-         "attn_decode_rows rejects a null pos");
-  EXPECT(jdt_attn_decode_rows(buf, buf, buf, buf, ip, 0, 2, 64, 128, .125f, nullptr) == 0,
-         "attn_decode_rows B = 0 is a no-op");
   EXPECT(jdt_embed_decode_rows(ip, buf, buf, buf, nullptr, 1, 128, 64, 8, nullptr) == -2,
          "embed_decode_rows rejects a null pos");
   EXPECT(jdt_embed_decode_rows(ip, buf, buf, buf, ip, 1, 0, 64, 8, nullptr) == -5, "embed_decode_rows rejects S_max 0");
@@ -182,108 +294,7 @@ int main() {
          "sample_rows rejects a null pos");
   EXPECT(jdt_sample_rows(buf, 8, 0, 8, 1.f, 0, 0, ip, 128, ip, ip, 3, 50, .9f, nullptr) == 0,
          "sample_rows B = 0 is a no-op");
-  // split-KV launchers: the same envelope up to 32768 rows, plus the workspace (1 x 2 x 3 chunks x 66 floats)
-  float* fp = reinterpret_cast<float*>(buf);
-  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, fp, 396, 1, 2, 32, 320, .125f, nullptr) == -3,
-         "attn_decode_long rejects head dim 32");
-  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, fp, 396, 1, 2, 64, 0, .125f, nullptr) == -4,
-         "attn_decode_long rejects S_max 0");
-  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, fp, 1L << 30, 1, 2, 64, 32769, .125f, nullptr) == -4,
-         "attn_decode_long rejects S_max 32769");
-  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, nullptr, 396, 1, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_decode_long rejects a null ws");
-  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, fp, 395, 1, 2, 64, 320, .125f, nullptr) == -10,
-         "attn_decode_long rejects a short ws");
-  EXPECT(jdt_attn_decode_long(buf, buf, buf, buf, ip, fp, 0, 0, 2, 64, 320, .125f, nullptr) == 0,
-         "attn_decode_long B = 0 is a no-op");
-  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, fp, 396, 1, 2, 32, 320, .125f, nullptr) == -3,
-         "attn_decode_long_rows rejects head dim 32");
-  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, fp, 396, 1, 2, 64, 0, .125f, nullptr) == -4,
-         "attn_decode_long_rows rejects S_max 0");
-  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, fp, 1L << 30, 1, 2, 64, 32769, .125f, nullptr) == -4,
-         "attn_decode_long_rows rejects S_max 32769");
-  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, nullptr, 396, 1, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_decode_long_rows rejects a null ws");
-  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, fp, 395, 1, 2, 64, 320, .125f, nullptr) == -10,
-         "attn_decode_long_rows rejects a short ws");
-  EXPECT(jdt_attn_decode_long_rows(buf, buf, buf, buf, ip, fp, 0, 0, 2, 64, 320, .125f, nullptr) == 0,
-         "attn_decode_long_rows B = 0 is a no-op");
-  // append launchers (attn_append.hip, embed_append): Dh = 64, S_max in 1..32768, C in 1..1024
-  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 1, 64, 2, 32, 320, .125f, nullptr) == -3,
-         "attn_append rejects head dim 32");
-  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 1, 64, 2, 64, 0, .125f, nullptr) == -4, "attn_append rejects S_max 0");
-  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 1, 64, 2, 64, 32769, .125f, nullptr) == -4,
-         "attn_append rejects S_max 32769");
-  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 1, 0, 2, 64, 320, .125f, nullptr) == -11, "attn_append rejects C 0");
-  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 1, 1025, 2, 64, 320, .125f, nullptr) == -11,
-         "attn_append rejects C 1025");
-  EXPECT(jdt_attn_append(buf, buf, nullptr, buf, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_append rejects null");
-  EXPECT(jdt_attn_append(buf, buf + 4, buf, buf, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
-         "attn_append rejects a misaligned cache");
-  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 65536, 64, 1, 64, 320, .125f, nullptr) == -5,
-         "attn_append rejects B * H past the grid");
-  EXPECT(jdt_attn_append(buf, buf, buf, buf, ip, 0, 64, 2, 64, 320, .125f, nullptr) == 0, "attn_append B = 0 is a no-op");
-  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, ip, ip, 1, 64, 2, 128, 320, .125f, nullptr) == -3,
-         "attn_append_rows rejects head dim 128");
-  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, ip, ip, 1, 64, 2, 64, 32769, .125f, nullptr) == -4,
-         "attn_append_rows rejects S_max 32769");
-  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, ip, ip, 1, 1025, 2, 64, 320, .125f, nullptr) == -11,
-         "attn_append_rows rejects C 1025");
-  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, ip, nullptr, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_append_rows rejects a null count");
-  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, nullptr, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_append_rows rejects a null pos");
-  EXPECT(jdt_attn_append_rows(buf + 4, buf, buf, buf, ip, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
-         "attn_append_rows rejects a misaligned qkv");
-  EXPECT(jdt_attn_append_rows(buf, buf, buf, buf, ip, ip, 0, 64, 2, 64, 320, .125f, nullptr) == 0,
-         "attn_append_rows B = 0 is a no-op");
-  // split-KV append launchers: the same envelope, plus the workspace (1 x 2 x 1 query tile x 1 span x 64 x 66 floats)
-  const long big = 1L << 40;   // a workspace size no shape here exceeds
-  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 8448, 1, 64, 2, 32, 320, .125f, nullptr) == -3,
-         "attn_append_split rejects head dim 32");
-  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 8448, 1, 64, 2, 64, 0, .125f, nullptr) == -4,
-         "attn_append_split rejects S_max 0");
-  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, big, 1, 64, 2, 64, 32769, .125f, nullptr) == -4,
-         "attn_append_split rejects S_max 32769");
-  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 8448, 1, 0, 2, 64, 320, .125f, nullptr) == -11,
-         "attn_append_split rejects C 0");
-  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, big, 1, 1025, 2, 64, 320, .125f, nullptr) == -11,
-         "attn_append_split rejects C 1025");
-  EXPECT(jdt_attn_append_split(buf, buf, nullptr, buf, ip, fp, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_append_split rejects null");
-  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, nullptr, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_append_split rejects a null ws");
-  EXPECT(jdt_attn_append_split(buf, buf + 4, buf, buf, ip, fp, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
-         "attn_append_split rejects a misaligned cache");
-  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, big, 65536, 64, 1, 64, 320, .125f, nullptr) == -5,
-         "attn_append_split rejects B * H past the grid");
-  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 8447, 1, 64, 2, 64, 320, .125f, nullptr) == -10,
-         "attn_append_split rejects a short ws");
-  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 2 * 8448 - 1, 1, 65, 2, 64, 320, .125f, nullptr) == -10,
-         "attn_append_split rejects a ws short of the second query tile");
-  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 2 * 8448 - 1, 1, 64, 2, 64, 513, .125f, nullptr) == -10,
-         "attn_append_split rejects a ws short of the second span");
-  EXPECT(jdt_attn_append_split(buf, buf, buf, buf, ip, fp, 0, 0, 64, 2, 64, 320, .125f, nullptr) == 0,
-         "attn_append_split B = 0 is a no-op");
-  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, 8448, 1, 64, 2, 128, 320, .125f, nullptr) == -3,
-         "attn_append_split_rows rejects head dim 128");
-  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, big, 1, 64, 2, 64, 32769, .125f, nullptr) == -4,
-         "attn_append_split_rows rejects S_max 32769");
-  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, big, 1, 1025, 2, 64, 320, .125f, nullptr) == -11,
-         "attn_append_split_rows rejects C 1025");
-  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, nullptr, fp, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_append_split_rows rejects a null count");
-  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, nullptr, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_append_split_rows rejects a null ws");
-  EXPECT(jdt_attn_append_split_rows(buf + 4, buf, buf, buf, ip, ip, fp, 8448, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
-         "attn_append_split_rows rejects a misaligned qkv");
-  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, big, 65536, 64, 1, 64, 320, .125f, nullptr) == -5,
-         "attn_append_split_rows rejects B * H past the grid");
-  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, 8447, 1, 64, 2, 64, 320, .125f, nullptr) == -10,
-         "attn_append_split_rows rejects a short ws");
-  EXPECT(jdt_attn_append_split_rows(buf, buf, buf, buf, ip, ip, fp, 0, 0, 64, 2, 64, 320, .125f, nullptr) == 0,
-         "attn_append_split_rows B = 0 is a no-op");
+  // embed_append: d % 8, C in 1..1024, S_max >= 1
   EXPECT(jdt_embed_append(ip, buf, buf, buf, ip, 1, 64, 128, 60, 8, nullptr) == -3, "embed_append rejects d % 8");
   EXPECT(jdt_embed_append(ip, buf, buf, buf, ip, 1, 0, 128, 64, 8, nullptr) == -11, "embed_append rejects C 0");
   EXPECT(jdt_embed_append(ip, buf, buf, buf, ip, 1, 64, 0, 64, 8, nullptr) == -5, "embed_append rejects S_max 0");
@@ -297,53 +308,8 @@ int main() {
          "embed_append_rows rejects C 1025");
   EXPECT(jdt_embed_append_rows(ip, buf, buf, buf, ip, ip, 0, 64, 128, 64, 8, nullptr) == 0,
          "embed_append_rows B = 0 is a no-op");
-  // FP8 KV cache launchers: the bf16 envelopes, null scales, 8-byte caches and 4-byte scales
+  // the FP8 prefill copy: null scales, 8-byte caches
   float* sp = reinterpret_cast<float*>(buf);
-  float* sp_mis = reinterpret_cast<float*>(buf + 2);
-  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, sp, sp, buf, ip, 1, 2, 32, 128, .125f, nullptr) == -3,
-         "attn_decode_fp8 rejects head dim 32");
-  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, sp, sp, buf, ip, 1, 2, 64, 129, .125f, nullptr) == -4,
-         "attn_decode_fp8 rejects S_max > 128");
-  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, nullptr, sp, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -2,
-         "attn_decode_fp8 rejects a null k_scale");
-  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, sp, nullptr, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -2,
-         "attn_decode_fp8 rejects a null v_scale");
-  EXPECT(jdt_attn_decode_fp8(buf, buf + 4, buf, sp, sp, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -6,
-         "attn_decode_fp8 rejects a cache off an 8-byte boundary");
-  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, sp, sp_mis, buf, ip, 1, 2, 64, 128, .125f, nullptr) == -6,
-         "attn_decode_fp8 rejects a misaligned scale");
-  EXPECT(jdt_attn_decode_fp8(buf, buf, buf, sp, sp, buf, ip, 0, 2, 64, 128, .125f, nullptr) == 0,
-         "attn_decode_fp8 B = 0 is a no-op");
-  EXPECT(jdt_attn_decode_fp8_rows(buf, buf, buf, sp, sp, buf, nullptr, 1, 2, 64, 128, .125f, nullptr) == -2,
-         "attn_decode_fp8_rows rejects null");
-  EXPECT(jdt_attn_decode_fp8_rows(buf, buf, buf, sp, sp, buf, ip, 0, 2, 64, 128, .125f, nullptr) == 0,
-         "attn_decode_fp8_rows B = 0 is a no-op");
-  EXPECT(jdt_attn_decode_fp8_long(buf, buf, buf, sp, sp, buf, ip, fp, 1L << 30, 1, 2, 64, 32769, .125f, nullptr) == -4,
-         "attn_decode_fp8_long rejects S_max > 32768");
-  EXPECT(jdt_attn_decode_fp8_long(buf, buf, buf, sp, nullptr, buf, ip, fp, 396, 1, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_decode_fp8_long rejects a null v_scale");
-  EXPECT(jdt_attn_decode_fp8_long(buf, buf, buf, sp, sp, buf, ip, fp, 395, 1, 2, 64, 320, .125f, nullptr) == -10,
-         "attn_decode_fp8_long rejects a short ws");
-  EXPECT(jdt_attn_decode_fp8_long(buf, buf, buf, sp, sp, buf, ip, fp, 0, 0, 2, 64, 320, .125f, nullptr) == 0,
-         "attn_decode_fp8_long B = 0 is a no-op");
-  EXPECT(jdt_attn_decode_fp8_long_rows(buf, buf, buf + 4, sp, sp, buf, ip, fp, 396, 1, 2, 64, 320, .125f, nullptr) == -6,
-         "attn_decode_fp8_long_rows rejects a cache off an 8-byte boundary");
-  EXPECT(jdt_attn_decode_fp8_long_rows(buf, buf, buf, sp, sp, buf, ip, fp, 395, 1, 2, 64, 320, .125f, nullptr) == -10,
-         "attn_decode_fp8_long_rows rejects a short ws");
-  EXPECT(jdt_attn_append_fp8(buf, buf, buf, sp, sp, buf, ip, 1, 64, 2, 32, 320, .125f, nullptr) == -3,
-         "attn_append_fp8 rejects head dim 32");
-  EXPECT(jdt_attn_append_fp8(buf, buf, buf, sp, sp, buf, ip, 1, 1025, 2, 64, 320, .125f, nullptr) == -11,
-         "attn_append_fp8 rejects C 1025");
-  EXPECT(jdt_attn_append_fp8(buf, buf, buf, nullptr, sp, buf, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_append_fp8 rejects a null k_scale");
-  EXPECT(jdt_attn_append_fp8(buf, buf + 4, buf, sp, sp, buf, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
-         "attn_append_fp8 rejects a cache off an 8-byte boundary");
-  EXPECT(jdt_attn_append_fp8(buf, buf, buf, sp, sp, buf, ip, 0, 64, 2, 64, 320, .125f, nullptr) == 0,
-         "attn_append_fp8 B = 0 is a no-op");
-  EXPECT(jdt_attn_append_fp8_rows(buf, buf, buf, sp, sp, buf, ip, nullptr, 1, 64, 2, 64, 320, .125f, nullptr) == -2,
-         "attn_append_fp8_rows rejects a null count");
-  EXPECT(jdt_attn_append_fp8_rows(buf, buf, buf, sp, sp_mis, buf, ip, ip, 1, 64, 2, 64, 320, .125f, nullptr) == -6,
-         "attn_append_fp8_rows rejects a misaligned scale");
   EXPECT(jdt_kv_quantize_rows(buf, buf, buf, sp, sp, 1, 2, 32, 128, 128, 16, nullptr) == -3,
          "kv_quantize_rows rejects head dim 32");
   EXPECT(jdt_kv_quantize_rows(buf, buf, buf, sp, sp, 1, 2, 64, 128, 64, 65, nullptr) == -5,
