@@ -603,6 +603,15 @@ struct PstRegs {
   float rbc1, rbc2;   // the step's AdamW bias corrections (computed during the previous barrier)
   float l_loss, l_corr;   // block (0,0): this thread's row loss / hit, folded into the metrics
 };
+// What a persistent launch reads once (pst_x_load) instead of every step: the batch does not
+// change inside a launch (the forward wrote X^T and the row-major copy before it), so the
+// lane's dW1 A fragments (xf), its next-forward A fragments (xa) and the label of its CE row
+// (row tid >> 2: four lanes per row) stay in registers.  Loaded by EVERY launch: a replay may
+// find a new batch in the same buffers.
+struct PstX {
+  bf16x8 xf[4], xa[4];
+  int lab;
+};
 // position of a step inside a persistent launch: step `it` of `n`, the launch counter
 // (Mlp2Args::ztick[2]) when the launch started
 struct PstPos {
@@ -612,6 +621,27 @@ struct PstPos {
   // every workgroup adds 1 to done[32 * column block]; null = the grid barrier form
   unsigned* done = nullptr;
 };
+// mlp2_bwd_body's batch operands (one step's phase 0, or once per persistent launch):
+// k-step ks of the A fragments of this wave's dW1 tile straight from X^T (written by
+// mlp2_fwd, zero-padded to Mp rows) ...
+template <int KC, bool SC1, class AT>
+__device__ __forceinline__ bf16x8 mlp2_xf_frag(AT& a, const int kc0, const int ks) {
+  const int lane = threadIdx.x & 63, wt_ = min((int)threadIdx.x >> 6, KC / 16 - 1), Mp = (a.M + 31) & ~31;
+  return __builtin_bit_cast(bf16x8, ld_b128<SC1>(a.XT + (long)(kc0 + wt_ * 16 + (lane & 15)) * a.ldxt +
+                                                 min(ks, Mp / 32 - 1) * 32 + 8 * (lane >> 4)));
+}
+// ... and of the A fragments of X[16w.., chunk] (row-major bf16 copy) for the next forward;
+// k past the chunk is multiplied by w1n's zero padding, so the address is only clamped
+template <int K_IN, class AT>
+__device__ __forceinline__ bf16x8 mlp2_xa_frag(AT& a, const int kc0, const int ks) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(
+             a.XR + (long)min(w * 16 + (lane & 15), a.M - 1) * K_IN + min(kc0 + ks * 32 + 8 * (lane >> 4), K_IN - 8)));
+}
+// lane j (a constant after unrolling) of this lane's quad, every lane active
+__device__ __forceinline__ float quad_lane(float v, int j) {
+  return j == 0 ? dpp_mov<0x00>(v) : j == 1 ? dpp_mov<0x55>(v) : j == 2 ? dpp_mov<0xAA>(v) : dpp_mov<0xFF>(v);
+}
 
 // AHEAD (single GPU, fused AdamW, W1^T copy): after its AdamW epilogue every
 // workgroup (blk, chunk) also computes the partial Z1 = X[:, chunk] W1'[chunk, blk]
@@ -629,10 +659,12 @@ struct PstPos {
 // is read with sc1 loads (never served by a stale L1; logits, re-armed write-through and
 // accumulated by atomics, come from the cross-XCD coherence point).
 template <int K_IN, int C, int KC, bool LOOP, bool AHEAD = false, bool TX = false, bool P3S = false,
-          bool FX = false, bool PST = false, class AT>
+          bool FX = false, bool PST = false, bool HX = false, class AT>
 __device__ __forceinline__ void mlp2_bwd_body(AT& a, const int bx, const int by, const int step_in,
-                                              PstRegs* R = nullptr, const PstPos pp = PstPos{0, 1, 0u}) {
+                                              PstRegs* R = nullptr, const PstPos pp = PstPos{0, 1, 0u},
+                                              const PstX* PX = nullptr) {
   static_assert(!PST || (AHEAD && !P3S && !LOOP), "persistent: the run-ahead step (one GPU, or TX / FX exchange)");
+  static_assert(PST || !HX, "HX: a persistent launch's batch fragments held in registers (PstX)");
   constexpr bool SCX = LOOP || PST;        // in-launch hand-offs: sc1 loads / stores
   // phase stamps: a persistent launch records step n-2 (a steady step: the last one also
   // stores the optimizer state)
@@ -670,6 +702,7 @@ __device__ __forceinline__ void mlp2_bwd_body(AT& a, const int bx, const int by,
   __shared__ __attribute__((aligned(16))) bf16_t h1T[16 * LDM];    // H1[:, blk]^T   (chunk-0 blocks)
   __shared__ __attribute__((aligned(16))) bf16_t dlT[16 * LDM];    // dlogits^T, classes padded to 16
   __shared__ float red[2][NW];
+  __shared__ float cel[2][PST ? MPM : 1];   // persistent lead: row loss / hit, from the CE's lanes to thread = row
   static_assert(!AHEAD || (!LOOP && KC <= 128 && KC % 16 == 0), "run-ahead: K chunk within 4 k-steps");
   constexpr int LDW1 = 128 + 8;            // w1n row: one hidden unit's KC inputs, zero-padded to 128
   constexpr int NCH = K_IN / KC;           // workgroups per column block
@@ -700,19 +733,43 @@ __device__ __forceinline__ void mlp2_bwd_body(AT& a, const int bx, const int by,
     step_lane = a.step[lz];
   }
   float lr0[C], lr1[C], lr2[AHEAD ? C : 1];
-  {
+  // persistent: the CE runs on the whole workgroup, four lanes per row -- lane cq of row
+  // crow loads, rounds and exponentiates the classes cq + 4k only (CK of them at most)
+  constexpr int CK = (C + 3) / 4;
+  const int crow = tid >> 2, cq = tid & 3;
+  float lown[CK];
+  if constexpr (PST) {
+    const long lo = (long)min(crow, M - 1) * C;
+    if (a.det_logits) {
+      // deterministic: this step's per-column-block partial logits (written through by the
+      // previous forward epilogues) summed in column-block order, per class as the one-step kernel
+      const float* pb = a.det_logits + (long)(step_in % 3) * (H / 16) * M * C + lo;
+#pragma unroll
+      for (int k = 0; k < CK; ++k) lown[k] = 0.f;
+      for (int q = 0; q < H / 16; ++q) {
+#pragma unroll
+        for (int k = 0; k < CK; ++k) lown[k] += ld_f<true>(pb + (long)q * M * C + min(cq + 4 * k, C - 1));
+      }
+    } else {
+      // accumulated by other XCDs' atomics during the previous step: sc1 loads of this
+      // step's buffer only (the step is known: no load waits on the counter)
+      const float* lg = a.logits + (long)(step_in % 3) * M * C + lo;
+#pragma unroll
+      for (int k = 0; k < CK; ++k) lown[k] = ld_f<true>(lg + min(cq + 4 * k, C - 1));
+    }
+  } else {
     const long lo = (long)min(tid, M - 1) * C;
     if (AHEAD && a.det_logits) {
-      // deterministic run-ahead / persistent: this step's per-column-block partial logits
-      // (step % 3 set, written by the previous forward epilogues -- write-through in a
-      // persistent launch) summed in column-block order; waits for the step (det mode only)
-      const int p3 = (PST ? step_in : step_lane) % 3;
+      // deterministic run-ahead: this step's per-column-block partial logits (step % 3 set,
+      // written by the previous forward epilogues) summed in column-block order; waits for
+      // the step (det mode only)
+      const int p3 = step_lane % 3;
       const float* pb = a.det_logits + (long)p3 * (H / 16) * M * C + lo;
 #pragma unroll
       for (int c = 0; c < C; ++c) lr0[c] = 0.f;
       for (int q = 0; q < H / 16; ++q) {
 #pragma unroll
-        for (int c = 0; c < C; ++c) lr0[c] += ld_f<PST>(pb + (long)q * M * C + c);
+        for (int c = 0; c < C; ++c) lr0[c] += pb[(long)q * M * C + c];
       }
 #pragma unroll
       for (int c = 0; c < C; ++c) {
@@ -722,20 +779,7 @@ __device__ __forceinline__ void mlp2_bwd_body(AT& a, const int bx, const int by,
     } else if constexpr (AHEAD) {   // step % 3 buffers, all three loaded (no wait on the step)
 #pragma unroll
       for (int c = 0; c < C; ++c) {
-        if constexpr (!PST) {
-          lr0[c] = a.logits[lo + c]; lr1[c] = a.logits[(long)M * C + lo + c]; lr2[c] = a.logits[2l * M * C + lo + c];
-        }
-      }
-      if constexpr (PST) {
-        // accumulated by other XCDs' atomics during the previous step: 8-byte sc1 loads of
-        // this step's buffer only (the step is known: no load waits on the counter)
-        static_assert(C % 2 == 0, "logits rows in 8-byte pairs");
-        const float* lg = a.logits + (long)(step_in % 3) * M * C + lo;
-#pragma unroll
-        for (int q = 0; q < C / 2; ++q) {
-          const unsigned long long x0 = ld_u64<true>(lg + 2 * q);
-          lr0[2 * q] = __uint_as_float((unsigned)x0); lr0[2 * q + 1] = __uint_as_float((unsigned)(x0 >> 32));
-        }
+        lr0[c] = a.logits[lo + c]; lr1[c] = a.logits[(long)M * C + lo + c]; lr2[c] = a.logits[2l * M * C + lo + c];
       }
     } else if constexpr (LOOP) {   // step known: this step's parity only
       const float* lg = a.logits + (long)(step_in & 1) * M * C;
@@ -757,7 +801,9 @@ __device__ __forceinline__ void mlp2_bwd_body(AT& a, const int bx, const int by,
       for (int c = 0; c < C; ++c) { lr0[c] = a.logits[lo + c]; lr1[c] = a.logits[(long)M * C + lo + c]; }
     }
   }
-  const int lab = a.labels[min(tid, M - 1)];
+  int lab;
+  if constexpr (PST) lab = PX->lab;   // of row crow
+  else lab = a.labels[min(tid, M - 1)];
   // G1 / H1: this thread's dropout group (rows 4rg..4rg+3, column j0+gn)
   const long go = ((long)min(rg, (M - 1) >> 2) * H + j0 + gn) * 4;
   const u32x4 g1q = ld_b128<SCX>(a.G1 + go);
@@ -769,9 +815,10 @@ __device__ __forceinline__ void mlp2_bwd_body(AT& a, const int bx, const int by,
   const int wt_ = min(w, NTILE - 1);
   bf16x8 xf[MPM / 32];
 #pragma unroll
-  for (int ks = 0; ks < MPM / 32; ++ks)
-    xf[ks] = __builtin_bit_cast(bf16x8, ld_b128<LOOP>(a.XT + (long)(kc0 + wt_ * 16 + (lane & 15)) * a.ldxt +
-                                                     min(ks, Mp / 32 - 1) * 32 + 8 * (lane >> 4)));
+  for (int ks = 0; ks < MPM / 32; ++ks) {
+    if constexpr (HX) xf[ks] = PX->xf[ks];   // the launch's batch: loaded once (pst_x_load)
+    else xf[ks] = mlp2_xf_frag<KC, LOOP>(a, kc0, ks);
+  }
   const long wo = (long)(j0 + (tid >> 5)) * C + min(tid & 31, C - 1);   // w2B[tid >> 5][tid & 31]
   bf16_t w2a, w2b;
   if constexpr (LOOP) {
@@ -849,9 +896,10 @@ __device__ __forceinline__ void mlp2_bwd_body(AT& a, const int bx, const int by,
   const int eg = g_lo + (tid >> 6), ee = (tid >> 4) & 3;
   if constexpr (AHEAD) {
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-      xa[ks] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(
-                   a.XR + (long)min(w * 16 + (lane & 15), M - 1) * K_IN + min(kc0 + ks * 32 + 8 * (lane >> 4), K_IN - 8)));
+    for (int ks = 0; ks < 4; ++ks) {
+      if constexpr (HX) xa[ks] = PX->xa[ks];
+      else xa[ks] = mlp2_xa_frag<K_IN>(a, kc0, ks);
+    }
   }
   __builtin_amdgcn_sched_barrier(0);
   int step = step_in;
@@ -861,8 +909,11 @@ __device__ __forceinline__ void mlp2_bwd_body(AT& a, const int bx, const int by,
   const int par = step & 1;
   float lrow[C];
   if constexpr (PST) {
+    // the row's rounded logits gathered from its four lanes (every lane active)
 #pragma unroll
-    for (int c = 0; c < C; ++c) lrow[c] = lr0[c];
+    for (int k = 0; k < CK; ++k) lown[k] = round_bf(lown[k]);
+#pragma unroll
+    for (int c = 0; c < C; ++c) lrow[c] = quad_lane(lown[c >> 2], c & 3);
   } else if constexpr (AHEAD) {
     const int p3 = step % 3;
 #pragma unroll
@@ -887,6 +938,52 @@ __device__ __forceinline__ void mlp2_bwd_body(AT& a, const int bx, const int by,
 
   // ---- 1. CE from the summed logits (rounded like the bf16 Dense output) -> dlogits
   float l_loss = 0.f, l_corr = 0.f;
+  if constexpr (PST) {
+    // Four lanes per row: every lane repeats the row's cheap serial parts (max / argmax over
+    // the gathered logits, the sum in class order, one log) and computes the transcendentals
+    // and bf16 dlogits of its own classes only -- the one-step kernel's values bit for bit
+    // (same operations on the same operands, sums in the same order).  The zero padding
+    // of dlB / dlT (classes >= C, rows >= M) is written by the launch's first step only:
+    // M does not change in a launch and no later phase writes these arrays.
+    float mx = -INFINITY;
+    int am = 0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      if (lrow[c] > mx) { mx = lrow[c]; am = c; }
+    }
+    float ex[CK];
+#pragma unroll
+    for (int k = 0; k < CK; ++k) ex[k] = __expf(lown[k] - mx);
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) s += quad_lane(ex[c >> 2], c & 3);
+    const float lse = mx + __logf(s);
+    if (crow < M) {
+#pragma unroll
+      for (int k = 0; k < CK; ++k) {
+        const int c = cq + 4 * k;
+        if (c < C) {
+          const bf16_t gb = f2bf((__expf(lown[k] - lse) - (c == lab ? 1.f : 0.f)) * a.inv_mb);
+          dlT[c * LDM + crow] = gb;
+          dlB[crow * LDB + c] = gb;
+        }
+      }
+      // the row's loss / hit go to thread = row (pst_metrics, the metric slots) after the barrier
+      if (lead && cq == 0) { cel[0][crow] = lse - lrow[lab]; cel[1][crow] = (am == lab) ? 1.f : 0.f; }
+    }
+    if (pp.it == 0) {
+      for (int idx = tid; idx < MPM * 32; idx += NT) {
+        const int r = idx >> 5, c = idx & 31;
+        if (r >= M || c >= C) dlB[r * LDB + c] = 0;
+      }
+      for (int idx = tid; idx < 16 * MPM; idx += NT) {
+        const int c = idx / MPM, r = idx % MPM;
+        if (r >= M || c >= C) dlT[c * LDM + r] = 0;
+      }
+    }
+    if ((tid & 31) < C) w2B[(tid >> 5) * LDB + (tid & 31)] = par ? w2b : w2a;
+    else if (pp.it == 0) w2B[(tid >> 5) * LDB + (tid & 31)] = 0;
+  } else {
   if (tid < M) {
     float mx = -INFINITY;
     int am = 0;
@@ -921,11 +1018,8 @@ __device__ __forceinline__ void mlp2_bwd_body(AT& a, const int bx, const int by,
   }
   for (int idx = tid; idx < (16 - C) * MPM; idx += NT) dlT[(C + idx / MPM) * LDM + idx % MPM] = 0;
   w2B[(tid >> 5) * LDB + (tid & 31)] = (tid & 31) < C ? (par ? w2b : w2a) : (bf16_t)0;
-  if constexpr (PST) {   // folded into the metrics while waiting in the grid barrier
-    R->l_loss = l_loss;
-    R->l_corr = l_corr;
   }
-  if (lead && (!PST || TX)) {   // persistent N > 1: the metric slots ride the exchange
+  if (lead && !PST) {
     l_loss = wave_sum(l_loss);
     l_corr = wave_sum(l_corr);
     if (lane == 0) { red[0][w] = l_loss; red[1][w] = l_corr; }
@@ -947,11 +1041,27 @@ __device__ __forceinline__ void mlp2_bwd_body(AT& a, const int bx, const int by,
     if (tid < 8)
       for (int i = t * 8 + tid; i < M * C; i += G * 8) st_f<true>(nxt + i, 0.f);
   }
-  if constexpr (AHEAD) {   // K padding of the W1' tile image
-    for (int idx = tid; idx < 16 * (128 - KC); idx += NT) w1n[(idx / (128 - KC)) * LDW1 + KC + idx % (128 - KC)] = 0;
+  if constexpr (AHEAD) {   // K padding of the W1' tile image (persistent: the first step's stays)
+    if (!PST || pp.it == 0)
+      for (int idx = tid; idx < 16 * (128 - KC); idx += NT) w1n[(idx / (128 - KC)) * LDW1 + KC + idx % (128 - KC)] = 0;
   }
   __syncthreads();
   STAMP(1);
+  if constexpr (PST) {
+    // the lead's rows' loss / hit, thread = row: folded into the metrics while waiting in
+    // the grid barrier (pst_metrics); N > 1: the metric slots ride the exchange
+    if (lead) {
+      l_loss = tid < M ? cel[0][tid] : 0.f;
+      l_corr = tid < M ? cel[1][tid] : 0.f;
+      R->l_loss = l_loss;
+      R->l_corr = l_corr;
+      if constexpr (TX) {
+        l_loss = wave_sum(l_loss);
+        l_corr = wave_sum(l_corr);
+        if (lane == 0) { red[0][w] = l_loss; red[1][w] = l_corr; }
+      }
+    }
+  }
 
   // ---- 2. dZ1 = (dlogits W2[blk]^T) * G1: one MFMA per wave (rows 16w.., K = classes);
   // the output lane layout (rows 4*(lane>>4)+e, column lane&15) is this thread's
@@ -1904,6 +2014,20 @@ __device__ __forceinline__ void pst_state_io(AT& a, const int bx, const int by, 
   }
 }
 
+// The batch operands a persistent launch keeps in registers (PstX): mlp2_bwd_body's phase-0
+// fragments at the same addresses, and the label of the lane's CE row.  by: the tile's chunk.
+template <int K_IN, int KC, bool HX, class AT>
+__device__ __forceinline__ void pst_x_load(AT& a, const int by, PstX& X) {
+  if constexpr (HX) {
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      X.xf[ks] = mlp2_xf_frag<KC, false>(a, by * KC, ks);
+      X.xa[ks] = mlp2_xa_frag<K_IN>(a, by * KC, ks);
+    }
+  }
+  X.lab = a.labels[min((int)threadIdx.x >> 2, a.M - 1)];
+}
+
 // Block (0,0), persistent launch: the step's loss sum / hits folded into the running metrics
 // ({loss sum, n, correct, n}: the per-step kernel's metric slot), between arriving at the grid
 // barrier and waiting on it (or after the last step) -- off the step's critical path.
@@ -1924,7 +2048,10 @@ __device__ __forceinline__ void pst_metrics(float* running, int M, const PstRegs
 // state of every workgroup's tile stays in registers across the steps (PstRegs) -- the
 // per-step reload and write-back of p / m / v (9.6 MB of L2 / HBM traffic a step) and the
 // launch ramp are gone; the last step stores the state, W1^T and the shadows as the
-// one-step kernel does.  Same arithmetic as n launches of mlp2_bwd_kernel<..., AHEAD>, up
+// one-step kernel does.  The batch is the launch's too: each lane's X fragments and CE label
+// are loaded before the first step (PstX; WPE = 4 keeps the per-step fragment loads, its
+// 128 VGPRs already spill), the zero padding of the step's LDS images is written by the
+// first step only, and the CE runs on four lanes per row.  Same arithmetic as n launches of mlp2_bwd_kernel<..., AHEAD>, up
 // to the arrival order of the memory-side logit atomics (fp32 sums in a different order):
 // tests/test_mlp2_persistent_gpu.py bounds the difference (median <= 1e-5 x the update
 // scale, p99.9 <= 1e-4 x).  Requires every workgroup
@@ -1969,6 +2096,9 @@ mlp2_pst_kernel(Mlp2Args a, int n, unsigned* ws, long long tmo) {
   KArgs* const kbase = (KArgs*)(__builtin_amdgcn_kernarg_segment_ptr());
   PstRegs R;
   pst_state_io<K_IN, C, KC, TX, Mlp2Args, FX>(a, bx, by, R, false);
+  R.l_loss = R.l_corr = 0.f;   // the lead's threads set them every step
+  PstX PX;
+  pst_x_load<K_IN, KC, WPE == 1>(a, by, PX);
   {
     const AdamK k0 = adam_consts(*kbase, step0);
     R.rbc1 = k0.rbc1;
@@ -1986,9 +2116,9 @@ mlp2_pst_kernel(Mlp2Args a, int n, unsigned* ws, long long tmo) {
     if (stw && it == n - 1) stw[7] = __builtin_amdgcn_s_memrealtime();
     // the tile coordinates re-made scalar each step: carried across the loop they may sit
     // in VGPRs, and the buffer resources built from them would become waterfall loops
-    mlp2_bwd_body<K_IN, C, KC, false, true, TX, false, FX, true>(
+    mlp2_bwd_body<K_IN, C, KC, false, true, TX, false, FX, true, WPE == 1>(
         *k, __builtin_amdgcn_readfirstlane(bx), __builtin_amdgcn_readfirstlane(by), step0 + it, &R,
-        PstPos{it, n, launch0, done});
+        PstPos{it, n, launch0, done}, &PX);
     if (stw && it == n - 2) stw[12] = __builtin_amdgcn_s_memrealtime();
     if (it + 1 < n) {
       if constexpr (CBW) {
